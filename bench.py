@@ -1,6 +1,14 @@
 """bench.py -- canonicalize+invert throughput on BASELINE.json's headline config (224x224x3, C8), 1..N GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: it builds the canonicalizer and its batches, warms up, times exactly K steps,
+writes the last timed step's outputs when --dump-outputs is given, and prints the line with `value` and `ms_per_step`.  Everything
+listed under "Extra objects" below (and the training, configs, tutorial and CPU-baseline legs) runs with --full only.
+`--dump-outputs DIR` writes what the last timed step handed its caller on rank 0, as float32 / float64 .npy files (under 64 MB):
+the canonicalized images and the inverted features of a fixed seeded sample of DUMP_IMAGES images of the batch, and the group
+index and activations of the whole batch.  Inputs and weights are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 `--gpus N` with N > 1 and no torch.distributed environment re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one process per GPU, RCCL =
@@ -17,7 +25,7 @@ network (ResNet-50) is NOT part of the headline.  Ranks shard the batch; the for
 collective, so scaling is weak (per-GPU batch fixed); W warm-up steps, then exactly K steps between
 barrier + synchronize pairs, max over ranks.
 
-Rank 0 prints ONE JSON line (contract in the task statement).  Extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement).  Extra objects (--full):
   roofline      HBM roofline of the dominant hand-written HBM kernel (the canonicalizing transform),
                 from HIP events recorded inside the timed region;
   roofline_dominant  the same object for the kernel the step spends most of its time in (the hand-written complex GEMM:
@@ -76,6 +84,43 @@ def build_canonicalizer(device, group_type: str = "rotation", num_rotations: int
     hp = types.SimpleNamespace(beta=1.0, input_crop_ratio=0.8, resize_shape=96)
     can = ea.GroupEquivariantImageCanonicalization(net, hp, (C, H, W))
     return can.to(device).eval()
+
+
+def headline_dtype(form: str) -> str:
+    """The line's `dtype` for the GEMM form the timed step's contraction ran in (fftconv.gemm_form)."""
+    if form == "h3":
+        return ("f32 (resampling / FFT / accumulation in fp32; the network's channel contraction as 2xfp16 split of every fp32 "
+                "operand (within one fp32 ulp), 3 exact products, fp32 accumulate -- closer to fp64 than the fp32 matrix "
+                "instruction, see step_ms_by_gemm_form)")
+    if form in ("6", "9"):
+        return (f"f32 (resampling / FFT / accumulation in fp32; the network's channel contraction as 3xbf16 exact split, "
+                f"{form} products, fp32 accumulate -- no further from fp64 than the fp32 matrix instruction, see step_ms_by_gemm_form)")
+    return "f32"
+
+
+DUMP_IMAGES = 32   # images of the batch whose pixels --dump-outputs writes: 2 x 32 x 602,112 B = 38.5 MB
+
+
+def dump_outputs(out_dir: str, y, inv, info: dict) -> dict:
+    """--dump-outputs: what the last timed step handed its caller -- canonicalized images, inverted features, group index and
+    activations -- as .npy files in `out_dir`.  The pixel outputs of a batch larger than DUMP_IMAGES are a fixed seeded sample
+    of its images; integers are written as float64 (exact), everything else as float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    B = y.shape[0]
+    pick = torch.arange(B)
+    if B > DUMP_IMAGES:
+        pick = torch.randperm(B, generator=torch.Generator().manual_seed(7))[:DUMP_IMAGES].sort().values
+    arrays = {"canonicalized_images": y[pick.to(y.device)], "inverted_features": inv[pick.to(inv.device)],
+              "group_index": info["group_index"], "group_activations": info["group_activations"]}
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.double() if (a.dtype == torch.float64 or not a.is_floating_point()) else a.float()
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": shapes, "images_sampled": pick.tolist()}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -757,7 +802,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per step")
     ap.add_argument("--mode", default="all", choices=["all", "forward", "train"],
-                    help="all: headline + train + configs legs in one line (default); forward: headline only; train: the DP training legs only")
+                    help="all: headline + train + configs legs in one line (default; without --full the headline alone); forward: headline "
+                         "only; train: the DP training legs only")
     ap.add_argument("--train-steps", type=int, default=8)
     ap.add_argument("--train-warmup", type=int, default=3)
     ap.add_argument("--train-batch", type=int, default=128, help="images per GPU per training step (reference: 128)")
@@ -769,7 +815,14 @@ def main():
                     help="forward mode without the group-action leg and the oracle check: every launch of a profiled run belongs to the timed "
                          "step (profiles/*/rocprofv3_kernel_stats_step.md)")
     ap.add_argument("--dry-run", action="store_true", help="launcher logic only, CPU + gloo, empty step")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: roofline / stages / GEMM forms / group-action leg, the oracle self check, "
+                         "the training, configs and tutorial legs, the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, float32 / float64, under 64 MB")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.mode == "train"):
+        ap.error("--dump-outputs writes the headline step's outputs: not with --dry-run or --mode train")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn_under_launcher(args.gpus))
@@ -808,7 +861,8 @@ def main():
                                    "parameterisation (bilinear-rotated banks; e2cnn's steerable basis is not restated -- e2cnn-trained weights enter "
                                    "via load_exported_dense), forward, then invert_canonicalization(scalar, 3ch); prediction network excluded",
                        "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world} (no collective in the forward path)"},
-            "rccl_ranks": world if comm.backend == "nccl" else 0, "backend": comm.backend, "ranks_share_gpu": comm.ranks_share_gpu}
+            "rccl_ranks": world if comm.backend == "nccl" else 0, "backend": comm.backend, "ranks_share_gpu": comm.ranks_share_gpu,
+            "full": args.full}
 
     if args.mode in ("all", "forward"):
         can = build_canonicalizer(dev)
@@ -816,12 +870,15 @@ def main():
         xs = [torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(rank * 16 + i)).to(dev) for i in range(NBUF)]
         fs = [torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(1000 + (rank * 16 + i) * 3)).to(dev) for i in range(NBUF)]
         it = [0]
+        keep = [None] if args.dump_outputs and rank == 0 else None   # the last step's outputs, held only when they are dumped
 
         def step():
             i = it[0] % NBUF
             it[0] += 1
             y = can(xs[i])
             out = can.invert_canonicalization(fs[i], induced_rep_type="scalar")
+            if keep is not None:
+                keep[0] = (y, out)
             return y, out
 
         with torch.no_grad():
@@ -836,6 +893,21 @@ def main():
             # `stages` run in a SECOND pass of the same K steps right after (round 6: ~10 brackets per step inside the value loop made
             # `value` slightly pessimistic -- VERDICT r05 weak 11); `ms_per_step_with_event_brackets` is that pass's wall time.
             elapsed, per_rank = comm.timed(step, args.steps, args.warmup)
+            if keep is not None:
+                line["dump_outputs"] = dump_outputs(args.dump_outputs, *keep[0], can.canonicalization_info_dict)
+                keep[0] = None
+            if not (args.full or args.step_only):
+                # a plain run ends here: the headline figure (and the outputs, when asked for) is all it measures
+                from equiadapt_amd.images.canonicalization_networks import fftconv as _fc
+
+                line.update({"value": B * world * args.steps / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
+                             "per_rank_ms_per_step": [t / args.steps * 1e3 for t in per_rank],
+                             "dtype": headline_dtype(_fc.LAST_FORM or _fc.gemm_form(256, 256)),
+                             "parity_ok": None, "parity_checked": {}})
+                if rank == 0:
+                    print(json.dumps(line), flush=True)
+                comm.close()
+                return
             kt = ops.KernelTimer()
             elapsed_kt, _ = comm.timed(step, args.steps, 0, kt)
             ktimes = kt.summary()
@@ -1007,13 +1079,7 @@ def main():
                                      "for callers that hold x and f at the same time, not what the library's two calls use)"},
             "self_check": self_check,
         })
-        if default_form == "h3":
-            line["dtype"] = ("f32 (resampling / FFT / accumulation in fp32; the network's channel contraction as 2xfp16 split of every fp32 "
-                             "operand (within one fp32 ulp), 3 exact products, fp32 accumulate -- closer to fp64 than the fp32 matrix "
-                             "instruction, see step_ms_by_gemm_form)")
-        elif default_form in ("6", "9"):
-            line["dtype"] = (f"f32 (resampling / FFT / accumulation in fp32; the network's channel contraction as 3xbf16 exact split, "
-                             f"{default_form} products, fp32 accumulate -- no further from fp64 than the fp32 matrix instruction, see step_ms_by_gemm_form)")
+        line["dtype"] = headline_dtype(default_form)
         line["stages"] = stage_table(ktimes, B)
         # the kernel the step spends most of its time in, against ITS roofline (the `roofline` object above is the metric's
         # HBM-bound transform kernel); traffic from the committed PMC profile when it is there

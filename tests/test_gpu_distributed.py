@@ -342,7 +342,7 @@ def test_bench_gpus_4_forward_over_gloo_on_one_gpu_prints_one_line():
     env = dict(os.environ, EQA_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--mode", "forward", "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--mode", "forward", "--full", "--steps", "3", "--warmup", "1",
                           "--batch", "64", "--check-images", "16"], capture_output=True, text=True, env=env, timeout=850)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -18,10 +18,10 @@ stats() {  # stats <name> <top_n> <command...>: per-kernel time table of a comma
 for w in $what; do
   case $w in
     bench)
-      python bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err"
+      python bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"
       ;;
     stats)
-      stats bench 16 python bench.py --mode forward --steps 20 --warmup 3 --no-cpu-baseline
+      stats bench 16 python bench.py --mode forward --full --steps 20 --warmup 3 --no-cpu-baseline
       stats train_images_canonicalizer 24 python tools/bench_train.py --batch 256 --steps 5
       stats train_images_leg 24 python bench.py --mode train --train-steps 5 --train-warmup 2 --no-cpu-baseline
       stats train_pointcloud 20 python tools/bench_train_pc.py --steps 20
@@ -35,7 +35,7 @@ for w in $what; do
       for set in "TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum" "GRBM_GUI_ACTIVE TCP_PENDING_STALL_CYCLES_sum" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum"; do
         i=$((i+1))
         rm -rf /tmp/pmc_$i
-        (cd /tmp && timeout 300 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_$i -o p -- python $GRAFT_REPO_ROOT/bench.py --mode forward --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
+        (cd /tmp && timeout 300 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_$i -o p -- python "$OLDPWD/bench.py" --mode forward --full --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
         python tools/pmc_summary.py /tmp/pmc_$i >> "$out/pmc_memory_path_raw.txt"
       done
       ;;

@@ -17,10 +17,10 @@ stats() {  # stats <name> <top_n> <command...>: per-kernel time table of a comma
 for w in $what; do
   case $w in
     bench)
-      python bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err"
+      python bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"
       ;;
     stats)
-      stats bench 16 python bench.py --mode forward --steps 20 --warmup 3 --no-cpu-baseline
+      stats bench 16 python bench.py --mode forward --full --steps 20 --warmup 3 --no-cpu-baseline
       stats step 10 python bench.py --mode forward --steps 20 --warmup 10 --step-only
       python bench.py --mode forward --steps 20 --warmup 10 --step-only > "$out/bench_step_only.json" 2>/dev/null
       stats tutorial_prior 28 python tools/bench_tutorial.py --leg prior --steps 5 --warmup 3

@@ -17,12 +17,12 @@ stats() {  # stats <name> <top_n> <command...>: per-kernel time table of a comma
 for w in $what; do
   case $w in
     bench)
-      python bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err"
+      python bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"
       ;;
     stats)
       stats step 10 python bench.py --mode forward --steps 20 --warmup 10 --step-only
       python bench.py --mode forward --steps 20 --warmup 10 --step-only > "$out/bench_step_only.json" 2>/dev/null
-      stats bench 16 python bench.py --mode forward --steps 20 --warmup 3 --no-cpu-baseline
+      stats bench 16 python bench.py --mode forward --full --steps 20 --warmup 3 --no-cpu-baseline
       EQA_LIFT_FFT_FUSED=0 EQA_LIFT_FFT_FORM=f32 EQA_FFT_GEMM_PIECES=f32 python bench.py --mode forward --steps 20 --warmup 10 --step-only > "$out/bench_step_only_round5_forms.json" 2>/dev/null
       EQA_LIFT_FFT_FORM=f32 EQA_FFT_GEMM_PIECES=6 python bench.py --mode forward --steps 20 --warmup 10 --step-only > "$out/bench_step_only_six_bf16_products.json" 2>/dev/null
       EQA_LIFT_FFT_FORM=f32 python bench.py --mode forward --steps 20 --warmup 10 --step-only > "$out/bench_step_only_fp32_lifting.json" 2>/dev/null
@@ -56,7 +56,7 @@ for w in $what; do
         python bench.py --mode forward --no-cpu-baseline > "$out/bench_forward_bare_$i.json" 2>/dev/null
         python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2957$i bench.py --gpus 1 --mode forward --no-cpu-baseline > "$out/bench_forward_rccl_world1_$i.json" 2> "$out/bench_forward_rccl_world1_$i.err"
       done
-      EQA_BENCH_BACKEND=gloo python bench.py --gpus 4 --mode forward --steps 5 --warmup 2 --batch 64 --check-images 16 > "$out/bench_gloo_world4_one_gpu.json" 2>/dev/null
+      EQA_BENCH_BACKEND=gloo python bench.py --gpus 4 --mode forward --full --steps 5 --warmup 2 --batch 64 --check-images 16 > "$out/bench_gloo_world4_one_gpu.json" 2>/dev/null
       python - "$out" <<'PY'
 import json, sys
 o = sys.argv[1]

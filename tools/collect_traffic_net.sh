@@ -7,7 +7,7 @@ out=${1:-gpurun_out/traffic_net}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --pmc $c -d "$out/$c" -o p --output-format csv -- python bench.py --mode forward --steps 3 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+  timeout 300 rocprofv3 --pmc $c -d "$out/$c" -o p --output-format csv -- python bench.py --mode forward --full --steps 3 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 done
 python - "$out" <<'PY'
 import csv, json, sys, collections

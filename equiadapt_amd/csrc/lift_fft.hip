@@ -38,13 +38,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef EQA_LF_CLOCK
-// Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of a column wave ([0..15]) and of a
-// convolution-only wave ([16..31]): tools/probe_lf_clock.py.
-__device__ unsigned long long g_lf_clock[32];
-#define LF_CLOCK_BEGIN() const bool lfc_on = blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (wave == 0 || wave == 1 || wave == 8); \
+// Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of five waves ([8 k .. 8 k + 7], k = slot:
+// waves 8, 1, 0, 6, 11), and HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD) -- tools/kbench_lift_fft.py.
+__device__ unsigned long long g_lf_clock[64];
+__device__ __forceinline__ int lf_clock_slot(int wave) { return wave == 8 ? 0 : wave == 1 ? 1 : wave == 0 ? 2 : wave == 6 ? 3 : wave == 11 ? 4 : -1; }
+#define LF_CLOCK_BEGIN() const bool lfc_on = blockIdx.x == 0 && (threadIdx.x & 63) == 0 && lf_clock_slot(wave) >= 0; \
+  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) { unsigned hw_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_)); g_lf_clock[40 + wave] = hw_; } \
   unsigned long long lfc_t = __builtin_readcyclecounter(); unsigned long long lfc_s[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
 #define LF_CLOCK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); lfc_s[i] += n_ - lfc_t; lfc_t = n_; } while (0)
-#define LF_CLOCK_END() do { if (lfc_on) for (int i_ = 0; i_ < 8; ++i_) g_lf_clock[8 * (ROLE == kConv ? 0 : (wave == 1 ? 1 : 2)) + i_] = lfc_s[i_]; } while (0)
+#define LF_CLOCK_END() do { if (lfc_on) for (int i_ = 0; i_ < 8; ++i_) g_lf_clock[8 * lf_clock_slot(wave) + i_] = lfc_s[i_]; } while (0)
 #else
 #define LF_CLOCK_BEGIN() do { } while (0)
 #define LF_CLOCK(i) do { } while (0)
@@ -105,7 +107,27 @@ __device__ __forceinline__ LfItem lf_item(unsigned work, int ngrp, int TY, int T
 //   kConv  waves 6..11: the convolution, 16 tile rows per sub-phase.  Waves w and w + 4 share a SIMD: 6 | 10 and 7 | 11 take 3 + 2 rows,
 //          8 and 9 (alone on their SIMDs) three each
 //   tail   all twelve waves: the row transforms (four consecutive rows x 16 channels per wave), then the column read (waves 0..5)
-enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2 only): waves 6, 7, 11 -- staging and row transforms, no convolution
+// FORM 2 deals them differently: waves 0..5 kCols; waves 8..11 kConv, one per SIMD (waves w, w + 4, w + 8 of a block share a SIMD:
+// HW_REG_HW_ID, profiles/r07/wave_simd.txt), nine of a sub-phase's 36 tiles each; waves 6 and 7 kRowp; waves 6..11 stage the
+// patches (lf_h2_rows: who transforms which rows).
+enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2 only): waves 6, 7 -- staging and row transforms, no convolution
+
+// FORM 2's row transforms.  Sub-phase s = 1..3 (waves 6, 7): a bit mask of the passes k (tile rows 12 (s - 1) + 4 k .. + 3) the
+// wave does beside the convolution; s = 4, the tail (any non-convolution wave): the first row of its pass, or -1.  The convolution
+// waves are the critical path of a sub-phase, and a row pass takes ~2.4 k cycles of the ~5 k of theirs: one pass per wave and
+// sub-phase fits beside them, two do not (profiles/r07).  So the third pass of every sub-phase waits for the tail, which then has
+// six passes on six waves, at most two per SIMD (waves w, w + 4, w + 8 share one).
+#ifdef EQA_LF_H2_ROWS_IN_SUB   // variant: the third pass alternates between waves 6 and 7, the tail keeps rows 36..47 (1.08 ms, not 1.02)
+__device__ __forceinline__ int lf_h2_rows(int wave, int s) {
+  if (s < 4) return wave == 6 ? (1 | ((s & 1) ? 4 : 0)) : (wave == 7 ? (2 | ((s & 1) ? 0 : 4)) : 0);
+  return wave == 6 ? 36 : wave == 7 ? 40 : wave == 4 ? 44 : -1;
+}
+#else
+__device__ __forceinline__ int lf_h2_rows(int wave, int s) {
+  if (s < 4) return wave == 6 ? 1 : (wave == 7 ? 2 : 0);
+  return wave == 6 ? 36 : wave == 7 ? 40 : wave == 0 ? 8 : wave == 4 ? 20 : wave == 1 ? 32 : wave == 5 ? 44 : -1;
+}
+#endif
 
 template <class F, int... Is>
 __device__ __forceinline__ void lf_for_const(F&& f, std::integer_sequence<int, Is...>) {
@@ -131,8 +153,8 @@ constexpr int kLpLdsBytes = kLfTileFloats * 4 + kLpPatchB;   // 160,704 bytes
 // back in the epilogue).  Two planes of 8 bytes per pixel are the fp32 patch's bytes + a third, so a sub-phase is TWELVE tile rows (a
 // ring of 16 patch rows; four sub-phases per item, where the three bf16 planes allowed four rows and needed twelve), and twelve
 // matrix instructions of 16 cycles per 16-pixel tile replace 19 of 32 on a datapath the transforms do not share: the convolution
-// waves are done in a third of a sub-phase, so THEY stage the patches (the column waves' loads queued behind their own stores:
-// 8.6 k cycles per item) and transform the previous sub-phase's rows; only twelve rows are left for the tail.
+// waves, not the column waves, stage the patches (the column waves' loads queued behind their own stores: 8.6 k cycles per item),
+// and two of them transform the previous sub-phase's rows; only twelve rows are left for the tail.
 //   K layout: a chunk = the pixel pair (j - 1 + 2 p, j + 2 p) of output pixel j, i.e. kx = 2 p - 1 (p = 0: weight 0), 2 p; the
 //   pair of p = 0, j = 0 starts 8 bytes in front of the row: the previous ring row's last pixel, and in front of the patch the tile
 //   buffer's last (never written, zeroed once) pad floats -- which is how the patch fits the CU's LDS to the byte.
@@ -512,18 +534,24 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
       asm volatile("" : "+v"(bias4));
     }
   };
-  // tile column t (16 pixels), tile rows y0 .. y0 + NROWS - 1 of the item (patch row R sits in ring slot R % 16)
-  auto conv_col_h = [&](const LfItem& it, int y0, int t, auto NR) {
+  // Nine tiles of a sub-phase: rows y0 .. y0 + 2 of tile column t0, then rows y1 .. y1 + 5 of tile column t1 (patch row R sits in ring
+  // slot R % 16).  A wave that stays in its column passes y1 = y0 + 3, t1 = t0 and cross = false; one that CROSSES to a new column
+  // re-reads the four rows of its register window that the first column's last row still used (the two behind them come from the
+  // new column already).
+  auto conv_col_h = [&](const LfItem& it, int y0, int t0, int y1, int t1, bool cross) {
     if constexpr (H2) {
-      constexpr int NROWS = decltype(NR)::value;
+      constexpr int NROWS = 9, SW = 3;
 #ifdef EQA_LF_H2_NOCONV    // ablation: the convolution waves without their convolution (the tile keeps what it held)
       return;
 #endif
-      const int base = (int)patch_b + (j - 1 + 2 * min(q, 2)) * 8 + t * 128;
-      lf_f16x8 win[7][2];                     // patch rows y0 + k in slot k % 7: five in use, two arriving (an LDS read comes back
-                                              // after 400-600 cycles while the row transforms and column reads queue beside it)
-      auto read_row = [&](int k) {
-        const int a = base + ((y0 + k) & (kLhRing - 1)) * kLhRowB;
+      const int base0 = (int)patch_b + (j - 1 + 2 * min(q, 2)) * 8 + t0 * 128;
+      const int base1 = base0 + (t1 - t0) * 128;
+      lf_f16x8 win[7][2];                     // the wave's patch rows k (below) in slot k % 7: five in use, two arriving (an LDS read
+                                              // comes back after 400-600 cycles while the row transforms and column reads queue beside it)
+      // the wave's k-th patch row: y0 + k of column t0 while the first column's rows need it (k < SW + 4), else y1 + k - SW of t1;
+      // NEW: the second column's reading of k (the re-read of k = SW .. SW + 3)
+      auto read_row = [&](int k, bool NEW) {
+        const int a = (NEW ? base1 + ((y1 + k - SW) & (kLhRing - 1)) * kLhRowB : base0 + ((y0 + k) & (kLhRing - 1)) * kLhRowB);
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
           // two 8-byte reads: the pixel pair sits at an 8-byte boundary (a 16-byte LDS read off a 16-byte boundary: ~200 cycles)
@@ -534,9 +562,9 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
         }
       };
 #pragma unroll
-      for (int k = 0; k < 6; ++k) read_row(k);
+      for (int k = 0; k < 6; ++k) read_row(k, false);
       const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-      const bool col_ok = it.gx0 + t * 16 + j < W1;
+      const bool col_ok0 = it.gx0 + t0 * 16 + j < W1, col_ok1 = it.gx0 + t1 * 16 + j < W1;
       // accumulators of two rows: a row's epilogue (scale, bias, relu, LDS write) sits BEHIND the next row's matrix instructions in
       // program order, so that it issues under them -- directly behind its own row it waited out the pipe's latency first, and the
       // wave issues in order: 39 cycles per matrix instruction instead of 16
@@ -546,14 +574,15 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
       // Per filter row the small products come first: (w lo, p hi), (w hi, p lo), then (w hi, p hi).
       f32x4 acc[2];
       f32x4 ev = zero;
-      // piece m of the epilogue of row rp: scale, bias, relu, mask, write
+      // piece m of the epilogue of the wave's row rp: scale, bias, relu, mask, write
       auto epi = [&](int m, int rp) {
-        const int y = y0 + rp;
+        const int y = rp < SW ? y0 + rp : y1 + rp - SW;
+        const int t = rp < SW ? t0 : t1;
         if (m == 0) ev = acc[rp & 1] * out_scale + bias4;
         else if (m == 1) { ev[0] = relu ? fmaxf(ev[0], 0.0f) : ev[0]; ev[1] = relu ? fmaxf(ev[1], 0.0f) : ev[1]; }
         else if (m == 2) { ev[2] = relu ? fmaxf(ev[2], 0.0f) : ev[2]; ev[3] = relu ? fmaxf(ev[3], 0.0f) : ev[3]; }
         else if (m == 3) {
-          const bool ok = col_ok && it.gy0 + y < H1;
+          const bool ok = (rp < SW ? col_ok0 : col_ok1) && it.gy0 + y < H1;
 #pragma unroll
           for (int k = 0; k < 4; ++k) ev[k] = ok ? ev[k] : 0.0f;
         } else if (m == 4) {
@@ -563,13 +592,18 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
       // The wave issues in order: what stands BETWEEN two matrix instructions is free, what stands behind a block of them is not.
 #pragma unroll
       for (int r = 0; r < NROWS; ++r) {
+        if (r == SW && cross) {       // wave-uniform
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int k = SW; k < SW + 4; ++k) read_row(k, true);
+        }
 #pragma unroll
         for (int m = 0; m < 15; ++m) {
           const int ky = m / 3, ch = m % 3;
           __builtin_amdgcn_sched_barrier(0);
           acc[r & 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ky][ch == 0 ? 1 : 0], win[(r + ky) % 7][ch == 1 ? 1 : 0], m == 0 ? zero : acc[r & 1], 0, 0, 0);
           if (r > 0 && m >= 2 && m < 7) epi(m - 2, r - 1);
-          if (m == 9 && r + 2 < NROWS) read_row(r + 6);
+          if (m == 9 && r + 2 < NROWS) read_row(r + 6, r + 6 >= SW + 4);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -756,12 +790,22 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
             cur_grp = it.grp;
           }
           if constexpr (H2) {
-            // waves 8, 9, 10: a tile column each of the sub-phase's twelve rows; waves 6, 7, 11: the row transform of four of the PREVIOUS
-            // sub-phase's rows each (the tail keeps rows 36..47)
+            // waves 8..11, one per SIMD: nine of the sub-phase's 36 tiles each, in column-major order (tile n: column n / 12, row n % 12)
+            // -- wave 8 column 0 rows 0..8, wave 11 column 2 rows 3..11; waves 9 and 10 three rows at the end / start of a column, then
+            // six of the middle column (a new column: a new register window).  Waves 6, 7: row transforms of the PREVIOUS
+            // sub-phase's rows (lf_h2_rows)
             if constexpr (ROLE == kConv) {
-              conv_col_h(it, kLhSubRows * sub, wave - 8, std::integral_constant<int, kLhSubRows>());
+              const int y = kLhSubRows * sub;
+              const bool cross = wave == 9 || wave == 10;
+              const int ya = y + (wave == 8 || wave == 10 ? 0 : (wave == 9 ? 9 : 3)), ta = wave == 8 || wave == 9 ? 0 : 2;
+              conv_col_h(it, ya, ta, cross ? y + (wave == 9 ? 0 : 6) : ya + 3, cross ? 1 : ta, cross);
             } else {
-              if (sub > 0) row_pass(kLhSubRows * (sub - 1) + 4 * (wave == 11 ? 2 : wave - 6));
+              if (sub > 0) {
+                const int a = lf_h2_rows(wave, sub);
+#pragma unroll 1
+                for (int k = 0; k < 3; ++k)
+                  if (a & (1 << k)) row_pass(kLhSubRows * (sub - 1) + 4 * k);
+              }
             }
           } else if constexpr (PIECES) {
             // the sub-phase's 12 tiles, three per SIMD: waves 8, 9 (alone on theirs) a row each, 6 | 10 and 7 | 11 share a row 2 + 1
@@ -829,8 +873,9 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
     if constexpr (PIECES) {
       if (live) row_pass(4 * wave);
     } else if constexpr (H2) {
-      if constexpr (ROLE == kRowp) {
-        if (live) row_pass(36 + 4 * (wave == 11 ? 2 : wave - 6));      // rows 36..47
+      if constexpr (ROLE != kConv) {
+        const int a = lf_h2_rows(wave, NSUB);
+        if (live && a >= 0) row_pass(a);
       }
     } else {
       if (live && wave < 8) row_pass(16 + 4 * wave);      // rows 16..47 (rows 0..15: waves 8, 9 during sub-phases 1, 2)
@@ -911,7 +956,7 @@ __global__ __launch_bounds__(kLfThreads) void lift5_fft48_fused_h2_kernel(const 
                                                                            int nxbound, float w_scale) {
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (w < 6) lift5_fft48_body<kCols, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
-  else if (w >= 8 && w <= 10) lift5_fft48_body<kConv, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
+  else if (w >= 8) lift5_fft48_body<kConv, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
   else lift5_fft48_body<kRowp, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
 }
 

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--channels", type=int, default=256)
     ap.add_argument("--size", type=int, default=96)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--h2-only", action="store_true", help="time the default (two fp16 pieces) form alone")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -62,8 +63,9 @@ def main():
     def lift_only():
         ops.lift_conv_grouped(x, wpk, bias, True, 5, 5)
 
-    for name, fn in (("fused eqa_lift5_fft48k5_input", fused), ("fused eqa_lift5_fft48k5_input_bf16x3", fused_p),
-                     ("eqa_absmax_slots + fused eqa_lift5_fft48k5_input_f16x2", fused_h), ("lift_conv_grouped + fft48k5_input_grouped", two), ("lift_conv_grouped alone", lift_only)):
+    forms = (("fused eqa_lift5_fft48k5_input", fused), ("fused eqa_lift5_fft48k5_input_bf16x3", fused_p),
+             ("eqa_absmax_slots + fused eqa_lift5_fft48k5_input_f16x2", fused_h), ("lift_conv_grouped + fft48k5_input_grouped", two), ("lift_conv_grouped alone", lift_only))
+    for name, fn in (forms[2:3] if a.h2_only else forms):
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
@@ -76,17 +78,26 @@ def main():
         print(f"{name:>56}: {e0.elapsed_time(e1) / a.reps:7.3f} ms per launch  (B = {B}, {C} channels, {S} x {S})")
     raw = ctypes.CDLL(_lib.SO_PATH)
     if hasattr(raw, "eqa_debug_lf_clock"):
-        out = (ctypes.c_ulonglong * 32)()
-        form = os.environ.get("EQA_LIFT_FFT_FORM")
+        # a clock build: [8 k .. 8 k + 7] the phases of the wave in slot k (older builds: the first three slots only), [40 + w] the
+        # HW_REG_HW_ID of wave w of block 0 (older builds: 0)
+        out = (ctypes.c_ulonglong * 64)()
+        form = os.environ.get("EQA_LIFT_FFT_FORM", "h2")
         (fused_p if form == "bf16x3" else fused_h if form == "h2" else fused)()
         torch.cuda.synchronize()
         assert raw.eqa_debug_lf_clock(out) == 0
         names = ["stage + barrier 1", "prefetch issue", "role work", "barrier 2", "tail row passes", "barrier 3", "column read", "barrier 4"]
         items = max(1, (M * (C // 16) + 255) // 256) if M * (C // 16) >= 256 else 1
-        for base, who in ((0, "convolution wave 8"), (8, "column wave 1"), (16, "column wave 0 (packed)")):
+        hw = [out[40 + w] for w in range(12)]
+        simd = {w: (hw[w] >> 4) & 3 for w in range(12)} if any(hw) else {}
+        for base, w, who in ((0, 8, "convolution wave 8"), (8, 1, "column wave 1"), (16, 0, "column wave 0 (packed)"),
+                             (24, 6, "row-transform wave 6"), (32, 11, "convolution wave 11")):
             tot = sum(out[base:base + 8])
-            print(f"{who}: cycles per item (block 0, {items} items): " + " | ".join(f"{n}: {out[base + i] // items}" for i, n in enumerate(names)) + f" | total {tot // items}")
-
+            if tot == 0:
+                continue
+            at = f" [SIMD {simd[w]}]" if simd else ""
+            print(f"{who}{at}: cycles per item (block 0, {items} items): " + " | ".join(f"{n}: {out[base + i] // items}" for i, n in enumerate(names)) + f" | total {tot // items}")
+        if simd:
+            print("block 0, HW_REG_HW_ID per wave: " + " ".join(f"w{w}:0x{hw[w]:x}(simd {simd[w]}, wave slot {hw[w] & 15}, cu {(hw[w] >> 8) & 15})" for w in range(12)))
 
 if __name__ == "__main__":
     main()

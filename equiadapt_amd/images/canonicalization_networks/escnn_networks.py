@@ -458,152 +458,134 @@ class ESCNNEquivariantNetwork(nn.Module):
         self._fold_cache[id(conv)] = (key, bank, bias)
         return bank, bias
 
-    def _winograd_filters(self, conv, bn, bank, m):
-        hit = self._fold_cache.get(("wino", m, id(conv)))
+    def _derived(self, conv, build, *tag):
+        """Something built from conv's folded bank (transformed filters, packed weights), cached under ``(*tag, id(conv))`` for as
+        long as `_folded`'s own entry for conv keeps its key."""
         key = self._fold_cache[id(conv)][0]
+        hit = self._fold_cache.get((*tag, id(conv)))
         if hit is None or hit[0] != key:
-            hit = (key, winograd.transform_filters(bank, m))
-            self._fold_cache[("wino", m, id(conv))] = hit
+            hit = (key, build())
+            self._fold_cache[(*tag, id(conv))] = hit
         return hit[1]
 
-    def _fft_filters(self, conv, bank):
-        hit = self._fold_cache.get(("fft", id(conv)))
-        key = self._fold_cache[id(conv)][0]
-        if hit is None or hit[0] != key:
-            hit = (key, fftconv.spectra_for_k(bank))
-            self._fold_cache[("fft", id(conv))] = hit
-        return hit[1]
+    @staticmethod
+    def _plain_5x5(conv) -> bool:
+        return not conv.lifting and conv.kernel_size == 5 and conv.stride == 1 and conv.padding == 0
 
-    def _lift_weights(self, conv, bank):
-        from equiadapt_amd import ops
+    @staticmethod
+    def _lift_kernel(conv, bank, h, narrow_unchecked: bool = False):
+        """Which hand-written lifting kernel takes conv on the map h: "narrow" (the fp32-MFMA implicit GEMM eqa_lift_conv_nhwc and the
+        forms built on it), "wide" (eqa_lift_conv_wide: 7 x 7 / 9 x 9 over RGB -- the reference tutorial's k = 9 -- and grayscale), or
+        None (the library).  ``narrow_unchecked``: the training forward, where `_training_fast_path_ok` has established stride 1 and
+        no padding for every layer, takes the narrow kernel on the shape test alone."""
+        if not conv.lifting or os.environ.get("EQA_LIFT_MFMA", "1") == "0":
+            return None
+        k, (cout, cin) = conv.kernel_size, bank.shape[:2]
+        unit = conv.stride == 1 and conv.padding == 0
+        if (unit or narrow_unchecked) and ops.lift_conv_supported(cin, k, k, cout):
+            return "narrow"
+        if (unit and h.is_contiguous(memory_format=torch.channels_last) and h.shape[-2] >= k and h.shape[-1] >= k
+                and ops.lift_conv_wide_supported(cin, k, k, cout)):
+            return "wide"
+        return None
 
-        hit = self._fold_cache.get(("lift", id(conv)))
-        key = self._fold_cache[id(conv)][0]
-        if hit is None or hit[0] != key:
-            narrow = ops.lift_conv_supported(bank.shape[1], bank.shape[-2], bank.shape[-1], bank.shape[0])
-            hit = (key, ops.pack_lift_weights(bank) if narrow else ops.pack_lift_weights_wide(bank))
-            self._fold_cache[("lift", id(conv))] = hit
-        return hit[1]
+    def _route(self, i, h, bank, convs, nhwc):
+        """(route, sums, m) of layer i of the inference path on the activation h (a channels-last or plain tensor, or the
+        `fftconv.GroupedMap` / `fftconv.LiftedInput` the previous layer left), decided from shapes alone: nothing is launched.
+        route: "fft5" | "fftk" | "wino" | "lift_fused" | "lift_grouped" | "lift" | "lift_wide" | "lib", in this order of precedence.
+        sums: the layer is the last before the tail and hands over the tail's window sums instead of its map.  m: Winograd's tile."""
+        conv, tail = convs[i], convs[-1]
+        cout, cin = bank.shape[:2]
+        k, kt = conv.kernel_size, tail.kernel_size
+        last_before_tail = i == len(convs) - 2
+        if nhwc and self._plain_5x5(conv) and fftconv.applicable(h, cin, cout):
+            # 5x5 regular->regular layer whose output the 44-pixel FFT tiles fit: overlap-save FFT convolution, 2.5 multiplies per
+            # output (Winograd F(4x4,5x5): 4)
+            return "fft5", (last_before_tail and kt in (3, 5) and tail.supports_linear_tail() and min(h.shape[-2:]) - 4 >= 2 * kt - 1), 0
+        if (nhwc and not conv.lifting and k != 5 and conv.stride == 1 and conv.padding == 0
+                and h.is_contiguous(memory_format=torch.channels_last) and fftconv.applicable_k(h.shape, cin, cout, k, h.device)):
+            # regular -> regular layer of another kernel size (the reference's tutorial network: k = 9): the same overlap-save FFT
+            # convolution with 49 - k outputs per tile (eqa_fft48_*); the linearised tail reads the map through the window-sum kernel
+            return "fftk", False, 0
+        if nhwc and self._plain_5x5(conv) and winograd.applicable(h, cin, cout):
+            # 5x5 regular->regular layer: Winograd F(m x m, 5x5), m = 4 where the size allows -- or 2 where only that lets the output
+            # transform emit the tail's window sums
+            m = winograd.tile_for(h)
+            if last_before_tail and not winograd.sums_applicable(h, kt, m) and winograd.sums_applicable(h, kt, 2):
+                m = 2
+            return "wino", last_before_tail and winograd.sums_applicable(h, kt, m), m
+        lift = self._lift_kernel(conv, bank, h) if nhwc else None
+        if lift == "narrow":
+            # If the next layer is an FFT-convolved 5x5 layer, it computes each tile of this map from its input patch inside its own
+            # forward transform (round 6: the layer does not run here at all); failing that the map goes out channel-group-major, the
+            # layout that layer's input transform reads in whole cache lines (it is consumed by nothing else).
+            nxt = convs[i + 1] if i + 1 < len(convs) - 1 else None
+            if nxt is not None and self._plain_5x5(nxt):
+                if fftconv.lift_fused_applicable(h.shape, bank.shape, nxt.out_channels * nxt.num_group_elements, h.device):
+                    return "lift_fused", False, 0
+                if fftconv.grouped_applicable((h.shape[0], cout, h.shape[2] - k + 1, h.shape[3] - k + 1), cout, cout, h.device):
+                    return "lift_grouped", False, 0
+            return "lift", False, 0
+        return ("lift_wide" if lift == "wide" else "lib"), False, 0
 
     def _forward_inference(self, x: torch.Tensor) -> torch.Tensor:
-        """eval + no_grad: conv(+folded BN) -> ReLU ... -> [last conv + group mean as window sums]."""
-        from equiadapt_amd import ops
-
+        """eval + no_grad: conv(+folded BN) -> ReLU ... -> [last conv + group mean as window sums].  Per layer: `_route` decides,
+        the loop body runs the route."""
         convs, norms = self._layers()
+        tail = convs[-1]
         nhwc = (self.out_channels * self.num_group_elements) % 4 == 0
         h = x.contiguous(memory_format=torch.channels_last) if nhwc else x
         pending = None  # bias of the previous layer whose (bias + ReLU) has not been applied to `h` yet
         for i, (conv, bn) in enumerate(zip(convs[:-1], norms)):
             bank, bias = self._folded(conv, bn)
-            last_before_tail = i == len(convs) - 2
-            is_5x5 = nhwc and not conv.lifting and conv.kernel_size == 5 and conv.stride == 1 and conv.padding == 0
-            if is_5x5 and fftconv.applicable(h, bank.shape[1], bank.shape[0]):
-                # 5x5 regular->regular layer whose output the 44-pixel FFT tiles fit: overlap-save FFT convolution, 2.5
-                # multiplies per output (Winograd F(4x4,5x5): 4).  Same fusions as below: the previous layer's bias + ReLU
-                # on the input loads, this layer's on the way out, window sums instead of the map in front of the tail.
-                tail = convs[-1]
-                Bf = self._fft_filters(conv, bank)
-                if last_before_tail and tail.kernel_size in (3, 5) and tail.supports_linear_tail() and \
-                        min(h.shape[-2:]) - 4 >= 2 * tail.kernel_size - 1:
-                    S = fftconv.conv5x5(h, Bf, bias, True, pending, pending is not None, sums_k=tail.kernel_size)
-                    return window_sums_to_activations(S, tail, h.shape[-2] - 4, h.shape[-1] - 4)
-                h = fftconv.conv5x5(h, Bf, bias, True, pending, pending is not None)
-                pending = None
-                if last_before_tail:
-                    return conv_then_group_pool(h, convs[-1])
-                continue
-            if isinstance(h, fftconv.GroupedMap):   # written for an FFT layer that did not take it after all
-                h = h.to_channels_last()
-            elif isinstance(h, fftconv.LiftedInput):
-                h = h.materialize()
-            if (nhwc and not conv.lifting and conv.kernel_size != 5 and conv.stride == 1 and conv.padding == 0
-                    and h.is_contiguous(memory_format=torch.channels_last)
-                    and fftconv.applicable_k(h.shape, bank.shape[1], bank.shape[0], conv.kernel_size, h.device)):
-                # regular -> regular layer of another kernel size (the reference's tutorial network: k = 9): the same overlap-save
-                # FFT convolution with 49 - k outputs per tile (eqa_fft48_*); previous layer's bias + ReLU on the input loads,
-                # this layer's on the way out; the linearised tail reads the map through the window-sum kernel
-                h = fftconv.conv_kxk(h, self._fft_filters(conv, bank), conv.kernel_size, bias, True, pending, pending is not None)
-                pending = None
-                if last_before_tail:
-                    return conv_then_group_pool(h, convs[-1])
-                continue
-            use_wino = is_5x5 and winograd.applicable(h, bank.shape[1], bank.shape[0])
-            if use_wino:
-                # 5x5 regular->regular layer: Winograd F(m x m, 5x5), m = 4 where the size allows.  The previous layer's
-                # bias + ReLU ride on its input loads, its own bias + ReLU on its output transform.
-                tail = convs[-1]
-                m = winograd.tile_for(h)
-                if last_before_tail and not winograd.sums_applicable(h, tail.kernel_size, m) and \
-                        winograd.sums_applicable(h, tail.kernel_size, 2):
-                    m = 2
-                if last_before_tail and winograd.sums_applicable(h, tail.kernel_size, m):
-                    # the activation of this layer is consumed only through the next layer's window sums: emit those
-                    # straight from the output transform, the feature map is never written
-                    S = winograd.conv5x5(h, self._winograd_filters(conv, bn, bank, m), bias, relu=True, in_bias=pending,
-                                         in_relu=pending is not None, sums_k=tail.kernel_size)
-                    return window_sums_to_activations(S, tail, h.shape[-2] - 4, h.shape[-1] - 4)
-                h = winograd.conv5x5(h, self._winograd_filters(conv, bn, bank, m), bias, relu=True,
-                                     in_bias=pending, in_relu=pending is not None)
-                pending = None
-                if last_before_tail:
-                    return conv_then_group_pool(h, convs[-1])
-                continue
-            if pending is not None:  # the next consumer cannot absorb it: apply in one fused pass
-                ops.bias_relu_nhwc_(h, pending)
-                pending = None
-            k = conv.kernel_size
-            if (nhwc and conv.lifting and conv.stride == 1 and conv.padding == 0 and os.environ.get("EQA_LIFT_MFMA", "1") != "0"
-                    and ops.lift_conv_supported(bank.shape[1], k, k, bank.shape[0])):
-                # lifting layer (RGB -> regular fields): hand-written fp32-MFMA implicit GEMM, bias + ReLU in its epilogue.
-                # If the next layer is an FFT-convolved 5x5 layer, the map goes out channel-group-major, the layout that
-                # layer's input transform reads in whole cache lines (it is consumed by nothing else).
-                nxt = convs[i + 1] if i + 1 < len(convs) - 1 else None
-                out_shape = (h.shape[0], bank.shape[0], h.shape[2] - k + 1, h.shape[3] - k + 1)
-                if (nxt is not None and not nxt.lifting and nxt.kernel_size == 5 and nxt.stride == 1 and nxt.padding == 0
-                        and fftconv.lift_fused_applicable(h.shape, bank.shape, nxt.out_channels * nxt.num_group_elements, h.device)):
-                    # round 6: the layer does not run here at all -- the FFT layer behind it computes each tile of this map from
-                    # its input patch inside its own forward transform (eqa_lift5_fft48k5_input)
-                    pieces = None
-                    if fftconv.LIFT_FFT_FORM == "bf16x3":     # the opt-in form's operand, cached per weight version like the folded bank
-                        hit = self._fold_cache.get(("liftp", id(conv)))
-                        key = self._fold_cache[id(conv)][0]
-                        if hit is None or hit[0] != key:
-                            hit = (key, fftconv.LiftedInput(h, bank, bias, True).pieces())
-                            self._fold_cache[("liftp", id(conv))] = hit
-                        pieces = hit[1]
-                    hit = None
-                    if fftconv.LIFT_FFT_FORM == "h2":         # the fp16 form's operand (and its scale: one host synchronisation per weight version)
-                        hit = self._fold_cache.get(("lifth", id(conv)))
-                        if hit is not None and hit[0] != self._fold_cache[id(conv)][0]:
-                            hit = None
-                    h = fftconv.LiftedInput(h, bank, bias, True, pieces, hit[1] if hit is not None else None)
-                    if fftconv.LIFT_FFT_FORM == "h2" and hit is None:
-                        self._fold_cache[("lifth", id(conv))] = (self._fold_cache[id(conv)][0], h.pieces_f16())
-                    continue
-                if (nxt is not None and not nxt.lifting and nxt.kernel_size == 5 and nxt.stride == 1 and nxt.padding == 0
-                        and fftconv.grouped_applicable(out_shape, bank.shape[0], bank.shape[0], h.device)):
-                    h = fftconv.GroupedMap(ops.lift_conv_grouped(h, self._lift_weights(conv, bank), bias, True, k, k))
-                    continue
-                h = ops.lift_conv_nhwc(h, self._lift_weights(conv, bank), bias, True, k, k)
-                if last_before_tail:
-                    return conv_then_group_pool(h, convs[-1])
-                continue
-            if (nhwc and conv.lifting and conv.stride == 1 and conv.padding == 0 and os.environ.get("EQA_LIFT_MFMA", "1") != "0"
-                    and h.shape[-2] >= k and h.shape[-1] >= k and ops.lift_conv_wide_supported(bank.shape[1], k, k, bank.shape[0])):
-                # the lifting filters the kernel above does not take (7 x 7 / 9 x 9 over RGB: the reference tutorial's k = 9; grayscale)
-                h = ops.lift_conv_wide(h, self._lift_weights(conv, bank), bias, True, k, k)
-                if last_before_tail:
-                    return conv_then_group_pool(h, convs[-1])
-                continue
-            if last_before_tail:
-                # bias + ReLU of this layer are applied inside the window-sum pass of the next (last) layer
-                c = F.conv2d(h, bank)
-                return conv_then_group_pool(c, convs[-1], shift=bias, relu=True)
-            h = F.conv2d(h, bank)
-            if nhwc and h.is_contiguous(memory_format=torch.channels_last):
-                pending = bias                                    # deferred: fused into whatever reads h next
+            route, sums, m = self._route(i, h, bank, convs, nhwc)
+            k, (H, W) = conv.kernel_size, h.shape[-2:]
+            last_before_tail, shift = i == len(convs) - 2, None
+            if route != "fft5" and isinstance(h, (fftconv.GroupedMap, fftconv.LiftedInput)):
+                h = h.materialize()                 # written for an FFT layer that did not take it after all
+            if route in ("fft5", "fftk", "wino"):
+                # the previous layer's bias + ReLU ride on the input loads, this layer's on the way out; in front of the tail the output
+                # transform emits the tail's window sums and the feature map is never written
+                in_bias, pending = pending, None
+                sums_k = tail.kernel_size if sums else 0
+                if route == "wino":
+                    U = self._derived(conv, lambda: winograd.transform_filters(bank, m), "wino", m)
+                    h = winograd.conv5x5(h, U, bias, relu=True, in_bias=in_bias, in_relu=in_bias is not None, sums_k=sums_k)
+                else:
+                    Bf = self._derived(conv, lambda: fftconv.spectra_for_k(bank), "fft")
+                    if route == "fft5":
+                        h = fftconv.conv5x5(h, Bf, bias, True, in_bias, in_bias is not None, sums_k=sums_k)
+                    else:
+                        h = fftconv.conv_kxk(h, Bf, k, bias, True, in_bias, in_bias is not None)
             else:
-                h = torch.relu_(h + bias[None, :, None, None])
+                if pending is not None:  # this consumer cannot absorb it: apply in one fused pass
+                    ops.bias_relu_nhwc_(h, pending)
+                    pending = None
+                if route == "lift_fused":
+                    operand = {}
+                    form = fftconv.LiftedInput.form_operand()     # the kernel form's packed filters, cached per weight version
+                    if form is not None:
+                        operand[form[1]] = self._derived(conv, lambda: form[2](bank), form[0])
+                    h = fftconv.LiftedInput(h, bank, bias, True, **operand)
+                elif route != "lib":                                  # the unfused lifting kernels: bias + ReLU in their epilogues
+                    pack = ops.pack_lift_weights_wide if route == "lift_wide" else ops.pack_lift_weights
+                    wpk = self._derived(conv, lambda: pack(bank), "lift")
+                    if route == "lift_grouped":
+                        h = fftconv.GroupedMap(ops.lift_conv_grouped(h, wpk, bias, True, k, k))
+                    else:
+                        h = (ops.lift_conv_wide if route == "lift_wide" else ops.lift_conv_nhwc)(h, wpk, bias, True, k, k)
+                else:
+                    h = F.conv2d(h, bank)
+                    if last_before_tail:
+                        shift = bias                                  # applied, with the ReLU, inside the tail's window-sum pass
+                    elif nhwc and h.is_contiguous(memory_format=torch.channels_last):
+                        pending = bias                                # deferred: fused into whatever reads h next
+                    else:
+                        h = torch.relu_(h + bias[None, :, None, None])
+            if sums:
+                return window_sums_to_activations(h, tail, H - k + 1, W - k + 1)
+            if last_before_tail:
+                return conv_then_group_pool(h, tail, shift=shift, relu=shift is not None)
         raise AssertionError("unreachable: the network always has at least two convolutions")
 
     # -- training fast path ------------------------------------------------------------------------------------
@@ -648,6 +630,7 @@ class ESCNNEquivariantNetwork(nn.Module):
         for li, (conv, bn, drop) in enumerate(zip(convs[:-1], norms, drops)):
             bank = conv.expanded_weights()
             part = None          # fp64 partial sums of the block's batch statistics, when the convolution kernel took them
+            lift = self._lift_kernel(conv, bank, h, narrow_unchecked=True)
             if not conv.lifting and conv.kernel_size == 5 and winograd.applicable(h, bank.shape[1], bank.shape[0]):
                 if (epilogue_stats and (bn.training or bn.running_mean is None) and winograd.Conv5x5Function.stats_supported(h, bank)):
                     h, part = winograd.Conv5x5Function.apply(h, bank, winograd.tile_for(h), True)
@@ -658,17 +641,14 @@ class ESCNNEquivariantNetwork(nn.Module):
                                            h.is_contiguous(memory_format=torch.channels_last))):
                 # kernel sizes Winograd F(m, 5) does not cover (the tutorial's k = 9): forward and both gradients as FFT convolutions
                 h = fftconv.ConvKxKFunction.apply(h, bank)
-            elif (conv.lifting and os.environ.get("EQA_LIFT_MFMA", "1") != "0"
-                  and ops.lift_conv_supported(bank.shape[1], conv.kernel_size, conv.kernel_size, bank.shape[0])):
+            elif lift == "narrow":
                 # batch statistics of the norm behind the layer: taken in the convolution's epilogue where the kernel has that form
                 if (epilogue_stats and (bn.training or bn.running_mean is None)
                         and ops.lift_conv_stats_supported(h.shape, conv.kernel_size, conv.kernel_size, bank.shape[0])):
                     h, part = LiftConvFunction.apply(h, bank, True)
                 else:
                     h = LiftConvFunction.apply(h, bank)
-            elif (conv.lifting and conv.stride == 1 and conv.padding == 0 and os.environ.get("EQA_LIFT_MFMA", "1") != "0"
-                  and h.is_contiguous(memory_format=torch.channels_last) and h.shape[-2] >= conv.kernel_size and h.shape[-1] >= conv.kernel_size
-                  and ops.lift_conv_wide_supported(bank.shape[1], conv.kernel_size, conv.kernel_size, bank.shape[0])):
+            elif lift == "wide":
                 h = LiftConvFunction.apply(h, bank)          # forward: eqa_lift_conv_wide; filter gradient: the framework's
             else:
                 h = F.conv2d(h, bank.contiguous(memory_format=torch.channels_last))

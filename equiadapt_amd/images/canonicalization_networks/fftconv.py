@@ -57,9 +57,16 @@ def gemm_form(cin: int, cout: int, bounded: bool = False) -> str:
         return GEMM_PIECES
     if bounded and f16_form_takes(cin, cout) and (GEMM_PIECES == "h3" or cin >= AUTO_MIN_CIN_H3):
         return "h3"
-    if GEMM_PIECES == "h3":        # no bound, or a shape the fp16 kernel does not take: as "auto" without it
-        return "6" if cin >= AUTO_MIN_CIN and cout % 128 == 0 else "f32"
+    # "auto", and "h3" without a bound or on a shape the fp16 kernel does not take
     return "6" if cin >= AUTO_MIN_CIN and cout % 128 == 0 else "f32"
+
+
+def f16_scale(t: torch.Tensor) -> float:
+    """The power of two that takes max |t| to at most 2^14: what an operand is multiplied by before it is split into fp16 pieces
+    (1 for an all-zero or non-finite t).  One host synchronisation when t is on the device."""
+    mx = float(t.abs().max().item())
+    ex = 14 - math.frexp(mx)[1] if 0.0 < mx < float("inf") else 0        # mx <= 2^frexp(mx)[1]
+    return math.ldexp(1.0, max(-100, min(100, ex)))
 
 
 class Spectra3M:
@@ -77,13 +84,11 @@ class Spectra3M:
         fragment order of the fp16 matrix instruction (built on first use: one host synchronisation for the maximum)."""
         if self._pieces_f16 is None:
             lib = _lib.load()
-            mx = float(self.data.abs().max().item())
-            ex = 14 - math.frexp(mx)[1] if 0.0 < mx < float("inf") else 0        # mx <= 2^frexp(mx)[1]
-            scale = math.ldexp(1.0, max(-100, min(100, ex)))
+            scale = f16_scale(self.data)
             bh = torch.empty(lib.eqa_fft48k5_spectra3m_f16_bytes(self.cin, self.cout) // 2, dtype=torch.int16, device=self.data.device)
             with torch.cuda.device(self.data.device):
                 _lib.check(lib.eqa_fft48k5_spectra3m_split_f16(self.data.data_ptr(), bh.data_ptr(), self.cin, self.cout, scale,
-                                                               torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_spectra3m_split_f16")
+                                                               ops._stream()), "eqa_fft48k5_spectra3m_split_f16")
             self._pieces_f16 = (bh, scale)
         return self._pieces_f16
 
@@ -93,7 +98,7 @@ class Spectra3M:
             bp = torch.empty(lib.eqa_fft48k5_spectra3m_bf16_bytes(self.cin, self.cout) // 2, dtype=torch.int16, device=self.data.device)
             with torch.cuda.device(self.data.device):
                 _lib.check(lib.eqa_fft48k5_spectra3m_split(self.data.data_ptr(), bp.data_ptr(), self.cin, self.cout,
-                                                           torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_spectra3m_split")
+                                                           ops._stream()), "eqa_fft48k5_spectra3m_split")
             self._pieces = bp
         return self._pieces
 
@@ -111,7 +116,7 @@ def filter_spectra3m(bank: torch.Tensor, correlate: bool = True) -> Spectra3M:
     B3 = torch.empty(lib.eqa_fft48k5_spectra3m_floats(Cin, Cout), dtype=torch.float32, device=bank.device)
     with torch.cuda.device(bank.device):
         _lib.check(lib.eqa_fft48k5_filter_spectra3m(bank.contiguous().data_ptr(), B3.data_ptr(), Cout, Cin, int(correlate),
-                                                    torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_filter_spectra3m")
+                                                    ops._stream()), "eqa_fft48k5_filter_spectra3m")
     return Spectra3M(B3, Cin, Cout)
 
 
@@ -137,15 +142,15 @@ def contract(V: torch.Tensor, B, M: int, vbound: Optional[torch.Tensor] = None) 
         if form == "h3":
             bh, b_scale = B.pieces_f16()
             _lib.check(lib.eqa_fft48k5_cgemm3m_f16x2(V.data_ptr(), bh.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, vbound.data_ptr(),
-                                                     vbound.numel(), b_scale, torch.cuda.current_stream().cuda_stream),
+                                                     vbound.numel(), b_scale, ops._stream()),
                        "eqa_fft48k5_cgemm3m_f16x2")
             return Mo
         if form in ("9", "6"):
             _lib.check(lib.eqa_fft48k5_cgemm3m_bf16x3(V.data_ptr(), B.pieces().data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, int(form),
-                                                      torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_cgemm3m_bf16x3")
+                                                      ops._stream()), "eqa_fft48k5_cgemm3m_bf16x3")
             return Mo
         _lib.check(lib.eqa_fft48k5_cgemm3m(V.data_ptr(), B.data.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout,
-                                           torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_cgemm3m")
+                                           ops._stream()), "eqa_fft48k5_cgemm3m")
         return Mo
     return torch.bmm(V, B, out=spectra_buffer(M, B.shape[2], dev))
 
@@ -160,8 +165,20 @@ def freq_index():
     return torch.cat([ky, eky]), torch.cat([kx, ekx])
 
 
+def tiles_k(n: int, k: int) -> int:
+    """Tiles along an axis of n input pixels for a k x k kernel: 49 - k outputs each."""
+    o = N + 1 - k
+    return 0 if n < k else (n - (k - 1) + o - 1) // o
+
+
 def tiles(n: int) -> int:
-    return 0 if n <= 4 else (n - 4 + OUT - 1) // OUT
+    return tiles_k(n, 5)
+
+
+def _stands_for_channels_last(self, memory_format=torch.contiguous_format) -> bool:
+    """`is_contiguous` of `GroupedMap` / `LiftedInput`: that of the tensor they turn into when no FFT layer takes them, so that a
+    consumer's applicability rule can be asked before anything is written."""
+    return memory_format == torch.channels_last
 
 
 class GroupedMap:
@@ -182,6 +199,8 @@ class GroupedMap:
         n, g, h, w, _ = self.data.shape
         return self.data.permute(0, 1, 4, 2, 3).reshape(n, g * 16, h, w).contiguous(memory_format=torch.channels_last)
 
+    materialize, is_contiguous = to_channels_last, _stands_for_channels_last
+
 
 class LiftedInput:
     """A lifting layer that has NOT run: (x channels-last (nimg, 3, H0, W0), folded 5 x 5 bank (C, 3, 5, 5) channels-last, bias (C),
@@ -200,48 +219,93 @@ class LiftedInput:
         self._pieces = pieces
         self._pieces_f16 = pieces_f16
 
-    def pieces_f16(self):
-        """(wh, w_scale): the folded bank as the operand of eqa_lift5_fft48k5_input_f16x2 -- (C, 2 pieces, 5 filter rows, 4 chunks, 8)
-        fp16 of w_scale * w (w_scale: the power of two that takes max |w| to at most 2^14); chunk p < 3 of filter row ky =
+    @staticmethod
+    def split_f16(bank: torch.Tensor):
+        """(wh, w_scale): a folded bank as the operand of eqa_lift5_fft48k5_input_f16x2 -- (C, 2 pieces, 5 filter rows, 4 chunks, 8)
+        fp16 of w_scale * w (w_scale: `f16_scale`); chunk p < 3 of filter row ky =
         [w(ci 0..2, kx = 2 p - 1), 0, w(ci 0..2, kx = 2 p), 0] (kx = -1: 0), chunk 3 = 0; pieces h1 = rn16(v), h2 = rn16(v - h1).
-        Built once per LiftedInput (one host synchronisation); the network caches it per weight version."""
+        One host synchronisation; the network caches it per weight version."""
+        w = bank.float()                                        # (C, 3, 5, 5) logical
+        C = w.shape[0]
+        scale = f16_scale(w)
+        wp = torch.zeros(C, 5, 8, 4, dtype=torch.float32, device=w.device)       # (co, ky, kx + 1 in 0..7, ci padded to 4)
+        wp[:, :, 1:6, :3] = w.permute(0, 2, 3, 1) * scale
+        chunks = wp.reshape(C, 5, 4, 8)
+        h1 = chunks.half()
+        h2 = (chunks - h1.float()).half()
+        return torch.stack([h1, h2], dim=1).contiguous(), scale
+
+    @staticmethod
+    def split_bf16(bank: torch.Tensor) -> torch.Tensor:
+        """A folded bank as the operand of eqa_lift5_fft48k5_input_bf16x3: (C, 3 pieces, 16 chunks, 8) bf16 -- chunk c < 15 = (filter
+        row c // 3, pixel pair c % 3): [w(ci 0..2, kx = 2 p), 0, w(ci 0..2, kx = 2 p + 1), 0] (kx = 5: 0), chunk 15 = 0; every value
+        split exactly into three bf16 pieces (the network caches it per weight version)."""
+        w = bank.float()                                        # (C, 3, 5, 5) logical
+        C = w.shape[0]
+        wp = torch.zeros(C, 5, 6, 4, dtype=torch.float32, device=w.device)       # (co, ky, kx padded to 6, ci padded to 4)
+        wp[:, :, :5, :3] = w.permute(0, 2, 3, 1)
+        chunks = torch.zeros(C, 16, 8, dtype=torch.float32, device=w.device)
+        chunks[:, :15] = wp.reshape(C, 5, 3, 8).reshape(C, 15, 8)
+        p0 = chunks.bfloat16()
+        r1 = chunks - p0.float()
+        p1 = r1.bfloat16()
+        p2 = (r1 - p1.float()).bfloat16()
+        assert torch.equal((p0.float() + p1.float()) + p2.float(), chunks), "the three bf16 pieces of a weight must add up exactly"
+        return torch.stack([p0, p1, p2], dim=1).contiguous()
+
+    @classmethod
+    def form_operand(cls):
+        """(cache tag, constructor keyword, builder from the folded bank) of the packed filter operand that the fused kernel reads in
+        the form LIFT_FFT_FORM names, for a caller that keeps it across LiftedInputs; None: the form reads the bank itself."""
+        return {"h2": ("lifth", "pieces_f16", cls.split_f16), "bf16x3": ("liftp", "pieces", cls.split_bf16)}.get(LIFT_FFT_FORM)
+
+    def pieces_f16(self):
+        """`split_f16` of this bank, built once per LiftedInput unless handed in."""
         if self._pieces_f16 is None:
-            w = self.bank.float()                                   # (C, 3, 5, 5) logical
-            C = w.shape[0]
-            mx = float(w.abs().max().item())
-            ex = 14 - math.frexp(mx)[1] if 0.0 < mx < float("inf") else 0
-            scale = math.ldexp(1.0, max(-100, min(100, ex)))
-            wp = torch.zeros(C, 5, 8, 4, dtype=torch.float32, device=w.device)       # (co, ky, kx + 1 in 0..7, ci padded to 4)
-            wp[:, :, 1:6, :3] = w.permute(0, 2, 3, 1) * scale
-            chunks = wp.reshape(C, 5, 4, 8)
-            h1 = chunks.half()
-            h2 = (chunks - h1.float()).half()
-            self._pieces_f16 = (torch.stack([h1, h2], dim=1).contiguous(), scale)
+            self._pieces_f16 = self.split_f16(self.bank)
         return self._pieces_f16
 
     def pieces(self) -> torch.Tensor:
-        """The folded bank as the operand of eqa_lift5_fft48k5_input_bf16x3: (C, 3 pieces, 16 chunks, 8) bf16 -- chunk c < 15 = (filter
-        row c // 3, pixel pair c % 3): [w(ci 0..2, kx = 2 p), 0, w(ci 0..2, kx = 2 p + 1), 0] (kx = 5: 0), chunk 15 = 0; every value
-        split exactly into three bf16 pieces (built once per LiftedInput; the network caches it per weight version)."""
+        """`split_bf16` of this bank, built once per LiftedInput unless handed in."""
         if self._pieces is None:
-            w = self.bank.float()                                   # (C, 3, 5, 5) logical
-            C = w.shape[0]
-            wp = torch.zeros(C, 5, 6, 4, dtype=torch.float32, device=w.device)       # (co, ky, kx padded to 6, ci padded to 4)
-            wp[:, :, :5, :3] = w.permute(0, 2, 3, 1)
-            chunks = torch.zeros(C, 16, 8, dtype=torch.float32, device=w.device)
-            chunks[:, :15] = wp.reshape(C, 5, 3, 8).reshape(C, 15, 8)
-            p0 = chunks.bfloat16()
-            r1 = chunks - p0.float()
-            p1 = r1.bfloat16()
-            p2 = (r1 - p1.float()).bfloat16()
-            assert torch.equal((p0.float() + p1.float()) + p2.float(), chunks), "the three bf16 pieces of a weight must add up exactly"
-            self._pieces = torch.stack([p0, p1, p2], dim=1).contiguous()
+            self._pieces = self.split_bf16(self.bank)
         return self._pieces
+
+    def spectra_into(self, V: torch.Tensor, B, st: int) -> Optional[torch.Tensor]:
+        """Write the tile spectra of the map this stands for into V (F, M, 2C), in the arithmetic LIFT_FFT_FORM names, on stream st.
+        Returns DCMAX_SLOTS floats whose maximum bounds |V| where the contraction with the spectra B will use them (non-negative
+        activations and the fp16 form "h3": the kernel hands over its DC bins), else None."""
+        lib = _lib.load()
+        nimg, C, H, W = self.shape
+        dims = (nimg, H + 4, W + 4, C, st)
+        px, pV = self.x.data_ptr(), V.data_ptr()
+        p_b = self.bias.data_ptr() if self.bias is not None else None
+        want_dc = self.relu and isinstance(B, Spectra3M) and gemm_form(B.cin, B.cout, True) == "h3"
+        vbound = None
+        if LIFT_FFT_FORM == "h2" and px % 16 == 0:      # (eqa_absmax_slots reads 16 bytes per lane)
+            wh, w_scale = self.pieces_f16()
+            xbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=self.device)
+            _lib.check(lib.eqa_absmax_slots(px, self.x.numel(), xbound.data_ptr(), st), "eqa_absmax_slots")
+            if want_dc:
+                vbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=self.device)
+            _lib.check(lib.eqa_lift5_fft48k5_input_f16x2(px, wh.data_ptr(), w_scale, xbound.data_ptr(), DCMAX_SLOTS, p_b, int(self.relu), pV,
+                                                         vbound.data_ptr() if want_dc else None, *dims), "eqa_lift5_fft48k5_input_f16x2")
+        elif LIFT_FFT_FORM == "bf16x3":                 # (this form has no variant that hands the DC bins over)
+            _lib.check(lib.eqa_lift5_fft48k5_input_bf16x3(px, self.pieces().data_ptr(), p_b, int(self.relu), pV, *dims),
+                       "eqa_lift5_fft48k5_input_bf16x3")
+        elif want_dc:
+            vbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=self.device)
+            _lib.check(lib.eqa_lift5_fft48k5_input_dcmax(px, self.bank.data_ptr(), p_b, 1, pV, vbound.data_ptr(), *dims),
+                       "eqa_lift5_fft48k5_input_dcmax")
+        else:
+            _lib.check(lib.eqa_lift5_fft48k5_input(px, self.bank.data_ptr(), p_b, int(self.relu), pV, *dims), "eqa_lift5_fft48k5_input")
+        return vbound
 
     def materialize(self) -> torch.Tensor:
         """The map itself, channels-last (the unfused lifting kernel) -- for a consumer that turned out not to be `conv5x5`."""
-        y = ops.lift_conv_nhwc(self.x, ops.pack_lift_weights(self.bank), self.bias, self.relu, 5, 5)
-        return y
+        return ops.lift_conv_nhwc(self.x, ops.pack_lift_weights(self.bank), self.bias, self.relu, 5, 5)
+
+    is_contiguous = _stands_for_channels_last
 
 
 # how the fused kernel multiplies: "h2" (default since the end of round 6) = two fp16 pieces per value, three exact products on the fp16
@@ -263,14 +327,13 @@ def lift_fused_applicable(x_shape, bank_shape, cout_next: int, device) -> bool:
     return x_shape[2] >= 5 and x_shape[3] >= 5 and grouped_applicable(out_shape, C, cout_next, device)
 
 
-def grouped_applicable(shape, cin: int, cout: int, device, max_waste: float = 1.12) -> bool:
-    """Would `conv5x5` take a (nimg, cin, H, W) fp32 map of this shape on `device` through the FFT path AND read it in the
-    grouped layout?  (Decided before the producing layer runs, so that it can write that layout.)"""
-    if not (ENABLED and device.type == "cuda" and len(shape) == 4 and shape[1] == cin and cin % 16 == 0):
-        return False
-    if os.environ.get("EQA_FFT_GROUPED", "1") == "0" or not _lib.load().eqa_fft48k5_input_grouped_supported(cin):
-        return False
-    if not gemm3m_supported(cin, cout) and ops.plane_gemm_supported(cin, cout):   # see `applicable`
+def _tiles_pay(shape, cin: int, cout: int, max_waste: float) -> bool:
+    """What `applicable` and `grouped_applicable` share: a contraction that is ours to run, enough tiles to amortise the filter spectra
+    (``MIN_TILES``), and tiles that fit the output to within ``max_waste`` (the FFT work is per tile: 88 outputs per axis = 2 tiles
+    exactly, 84 would waste 5 %, 50 would waste 43 % -> Winograd)."""
+    if shape[1] != cin or (not gemm3m_supported(cin, cout) and ops.plane_gemm_supported(cin, cout)):
+        # (e.g. 32 output channels: the complex GEMM wants 64-column tiles, the Winograd planes' GEMM takes 32 -- the path whose
+        # contraction is hand-written wins over the one that would call the library)
         return False
     H, W = shape[-2:]
     if H < 16 or W < 16 or shape[0] * tiles(H) * tiles(W) < MIN_TILES:
@@ -278,25 +341,23 @@ def grouped_applicable(shape, cin: int, cout: int, device, max_waste: float = 1.
     return tiles(H) * OUT <= max_waste * (H - 4) and tiles(W) * OUT <= max_waste * (W - 4)
 
 
+def grouped_applicable(shape, cin: int, cout: int, device, max_waste: float = 1.12) -> bool:
+    """Would `conv5x5` take a (nimg, cin, H, W) fp32 map of this shape on `device` through the FFT path AND read it in the
+    grouped layout?  (Decided before the producing layer runs, so that it can write that layout.)"""
+    if not (ENABLED and device.type == "cuda" and len(shape) == 4 and cin % 16 == 0):
+        return False
+    if os.environ.get("EQA_FFT_GROUPED", "1") == "0" or not _lib.load().eqa_fft48k5_input_grouped_supported(cin):
+        return False
+    return _tiles_pay(shape, cin, cout, max_waste)
+
+
 def applicable(x: torch.Tensor, cin: int, cout: int, max_waste: float = 1.12) -> bool:
-    """Channels-last fp32 device tensor, 5x5 kernel, enough tiles to amortise the filter spectra (``MIN_TILES``), and tiles
-    that fit the output to within ``max_waste`` (the FFT work is per tile: 88 outputs per axis = 2 tiles exactly, 84 would
-    waste 5 %, 50 would waste 43 % -> Winograd)."""
+    """Should `conv5x5` take x: a channels-last fp32 device tensor (or a map standing in its place) that `_tiles_pay`."""
     if isinstance(x, (GroupedMap, LiftedInput)):
         return grouped_applicable(x.shape, cin, cout, x.device, max_waste)
     if not (ENABLED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
         return False
-    H, W = x.shape[-2:]
-    if H < 16 or W < 16 or x.shape[1] != cin:
-        return False
-    if not gemm3m_supported(cin, cout) and ops.plane_gemm_supported(cin, cout):
-        # (e.g. 32 output channels: the complex GEMM wants 64-column tiles, the Winograd planes' GEMM takes 32 -- the path whose
-        # contraction is hand-written wins over the one that would call the library)
-        return False
-    oh, ow = H - 4, W - 4
-    if x.shape[0] * tiles(H) * tiles(W) < MIN_TILES:
-        return False
-    return tiles(H) * OUT <= max_waste * oh and tiles(W) * OUT <= max_waste * ow
+    return _tiles_pay(x.shape, cin, cout, max_waste)
 
 
 def _order(C: int, G: int) -> torch.Tensor:
@@ -320,7 +381,7 @@ def filter_spectra(bank: torch.Tensor, groups=None, correlate: bool = True) -> t
         B = torch.empty((F, 2 * Cin, 2 * Cout), dtype=torch.float32, device=bank.device)
         with torch.cuda.device(bank.device):
             _lib.check(lib.eqa_fft48k5_filter_spectra(bank.contiguous().data_ptr(), B.data_ptr(), Cout, Cin, int(correlate),
-                                                      torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_filter_spectra")
+                                                      ops._stream()), "eqa_fft48k5_filter_spectra")
         return B
     assert correlate, "the host construction is the correlation (forward) form"
     gin, gout = groups if groups is not None else group_sizes(Cin, Cout)
@@ -351,165 +412,29 @@ def output_stats_supported(nimg: int, OH: int, OW: int, cout: int) -> bool:
     return _lib.load().eqa_fft48k5_output_stats_rows(nimg, OH, OW, cout) > 0
 
 
-def conv5x5(x: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor], relu: bool,
-            in_bias: Optional[torch.Tensor] = None, in_relu: bool = False, sums_k: int = 0,
-            keep_V: Optional[list] = None, stats: Optional[list] = None) -> torch.Tensor:
-    """x: channels-last (nimg,Cin,H,W) -> channels-last (nimg,Cout,H-4,W-4) = [relu](conv2d(act(x), g) + bias) with
-    B = spectra_for(g) (either form) and act(x) = [relu](x + in_bias[c]) applied while loading; ``sums_k`` > 0: return instead the
-    (nimg, Cout, sums_k, sums_k) fp64 window sums of that output (the linearised last layer consumes only those).
-    ``keep_V``: a list that receives the input spectra V (training: the filter gradient reuses them).  ``stats``: a list that
-    receives the (rows, Cout, 2) fp64 partial sums of the output's per-channel sum / sum of squares, taken by the inverse
-    transform (training, no bias / activation; the caller checks ``output_stats_supported``)."""
-    lib = _lib.load()
-    nimg, Cin, H, W = x.shape
-    if isinstance(B, Spectra3M):
-        Cout = B.cout
-        assert B.cin == Cin
-    else:
-        Cout = B.shape[2] // 2
-        assert B.shape == (F, 2 * Cin, 2 * Cout)
-    OH, OW = H - 4, W - 4
-    TY, TX = tiles(H), tiles(W)
-    M = nimg * TY * TX
-    dev = x.device
-    st = torch.cuda.current_stream().cuda_stream
-    V = spectra_buffer(M, 2 * Cin, dev)
-    p_in_bias = in_bias.data_ptr() if in_bias is not None else None
-    p_bias = bias.data_ptr() if bias is not None else None
-    vbound = None
-    with torch.cuda.device(dev):
-        if isinstance(x, LiftedInput):
-            assert in_bias is None and not in_relu
-            with _timed("lift_fft_input"):
-                p_b = x.bias.data_ptr() if x.bias is not None else None
-                if LIFT_FFT_FORM == "h2" and x.x.data_ptr() % 16 == 0:      # (eqa_absmax_slots reads 16 bytes per lane)
-                    wh, w_scale = x.pieces_f16()
-                    xbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=dev)
-                    _lib.check(lib.eqa_absmax_slots(x.x.data_ptr(), x.x.numel(), xbound.data_ptr(), st), "eqa_absmax_slots")
-                    want_dc = x.relu and isinstance(B, Spectra3M) and gemm_form(Cin, Cout, True) == "h3"
-                    if want_dc:
-                        vbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=dev)
-                    _lib.check(lib.eqa_lift5_fft48k5_input_f16x2(x.x.data_ptr(), wh.data_ptr(), w_scale, xbound.data_ptr(), DCMAX_SLOTS, p_b,
-                                                                 int(x.relu), V.data_ptr(), vbound.data_ptr() if want_dc else None, nimg,
-                                                                 H + 4, W + 4, Cin, st), "eqa_lift5_fft48k5_input_f16x2")
-                elif LIFT_FFT_FORM == "bf16x3":
-                    _lib.check(lib.eqa_lift5_fft48k5_input_bf16x3(x.x.data_ptr(), x.pieces().data_ptr(), p_b, int(x.relu), V.data_ptr(), nimg,
-                                                                  H + 4, W + 4, Cin, st), "eqa_lift5_fft48k5_input_bf16x3")
-                elif x.relu and isinstance(B, Spectra3M) and gemm_form(Cin, Cout, True) == "h3":
-                    # non-negative activations: the kernel also hands over its DC bins, the bound the fp16 contraction scales by
-                    vbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=dev)
-                    _lib.check(lib.eqa_lift5_fft48k5_input_dcmax(x.x.data_ptr(), x.bank.data_ptr(), p_b, 1, V.data_ptr(), vbound.data_ptr(),
-                                                                 nimg, H + 4, W + 4, Cin, st), "eqa_lift5_fft48k5_input_dcmax")
-                else:
-                    _lib.check(lib.eqa_lift5_fft48k5_input(x.x.data_ptr(), x.bank.data_ptr(), p_b, int(x.relu), V.data_ptr(), nimg, H + 4, W + 4,
-                                                           Cin, st), "eqa_lift5_fft48k5_input")
-        else:
-            T = torch.empty(max(lib.eqa_fft48k5_workspace_bytes(nimg, H, OW, Cin), 4) // 4, dtype=torch.float32, device=dev)
-            with _timed("fft_input"):
-                fn = lib.eqa_fft48k5_input_grouped if isinstance(x, GroupedMap) else lib.eqa_fft48k5_input
-                _lib.check(fn(x.data_ptr(), T.data_ptr(), V.data_ptr(), p_in_bias, int(in_relu), nimg, H, W, Cin, st), "eqa_fft48k5_input")
-            del T
-        with _timed("fft_gemm"):
-            Mo = contract(V, B, M, vbound)
-        if keep_V is not None:
-            keep_V.append(V)
-        del V
-        T2 = torch.empty(max(lib.eqa_fft48k5_workspace_bytes(nimg, OH, OW, Cout), 4) // 4, dtype=torch.float32, device=dev)
-        if sums_k:
-            S = torch.empty((nimg, Cout, sums_k, sums_k), dtype=torch.float64, device=dev)
-            ws = torch.empty(nimg * OH * TX * Cout * (2 * sums_k - 1), dtype=torch.float32, device=dev)
-            with _timed("fft_output_sums"):
-                _lib.check(lib.eqa_fft48k5_output_sums(Mo.data_ptr(), T2.data_ptr(), p_bias, int(relu), S.data_ptr(), ws.data_ptr(),
-                                                       nimg, OH, OW, Cout, sums_k, st), "eqa_fft48k5_output_sums")
-            return S
-        y = torch.empty((nimg, Cout, OH, OW), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        if stats is not None:
-            assert bias is None and not relu
-            part = torch.empty((lib.eqa_fft48k5_output_stats_rows(nimg, OH, OW, Cout), Cout, 2), dtype=torch.float64, device=dev)
-            with _timed("fft_output"):
-                _lib.check(lib.eqa_fft48k5_output_stats(Mo.data_ptr(), T2.data_ptr(), y.data_ptr(), part.data_ptr(), nimg, OH, OW, Cout, st),
-                           "eqa_fft48k5_output_stats")
-            stats.append(part)
-            return y
-        with _timed("fft_output"):
-            _lib.check(lib.eqa_fft48k5_output(Mo.data_ptr(), T2.data_ptr(), p_bias, int(relu), y.data_ptr(), nimg, OH, OW, Cout, st),
-                       "eqa_fft48k5_output")
-        return y
-
-
-def filter_grad(V: torch.Tensor, dy: torch.Tensor, cin: int, G: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """d loss / d filter bank (Cout, Cin, 5, 5) of y = conv2d(x, bank) from V = the spectra of x's tiles (``keep_V`` of the
-    forward pass) and the output gradient dy (channels-last): spectra of the disjoint 44 x 44 gradient tiles, one batched GEMM
-    over the tiles per frequency (D[f] = V[f]^T G[f]), and the inverse transform restricted to the 5 x 5 support
-    (eqa_fft48k5_grad_transform / _filter_grad).  2.5 multiplies per output as in the forward pass; Winograd's filter gradient
-    (`winograd.filter_grad`) needs 4 and a 4x larger transformed gradient."""
-    lib = _lib.load()
-    nimg, Cout, OH, OW = dy.shape
-    dev = dy.device
-    M = V.shape[1]
-    assert V.shape == (F, M, 2 * cin) and M == nimg * tiles(OH + 4) * tiles(OW + 4)
-    st = torch.cuda.current_stream().cuda_stream
-    if G is None:
-        G = grad_spectra(dy)
-    dbank = torch.empty((Cout, cin, 5, 5), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if GEMM == "3m" and lib.eqa_fft48k5_wgrad3m_supported(cin, Cout) and os.environ.get("EQA_FFT_WGRAD3M", "1") != "0":
-            # the contraction over the tiles in the 3-multiplication form on the fp32 MFMA (the library's real GEMM: 4 products)
-            D = torch.empty((F, cin, 2, Cout), dtype=torch.float32, device=dev)      # Dr | Di per input channel
-            _lib.check(lib.eqa_fft48k5_wgrad3m(V.data_ptr(), G.data_ptr(), D.data_ptr(), M, cin, Cout, st), "eqa_fft48k5_wgrad3m")
-            _lib.check(lib.eqa_fft48k5_filter_grad3m(D.data_ptr(), dbank.data_ptr(), Cout, cin, st), "eqa_fft48k5_filter_grad3m")
-            return dbank
-        D = torch.bmm(V.transpose(1, 2), G)                       # (F, 2 Cin, 2 Cout)
-        _lib.check(lib.eqa_fft48k5_filter_grad(D.data_ptr(), dbank.data_ptr(), Cout, cin, st), "eqa_fft48k5_filter_grad")
-    return dbank
-
-
-def input_grad(dy: torch.Tensor, bank: torch.Tensor, G: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """d loss / d x (channels-last (nimg, Cin, OH+4, OW+4)) of y = conv2d(x, bank): the full convolution of dy with the
-    filters, tile by tile in the frequency domain with overlap-add (eqa_fft48k5_input_grad).  ``G``: the gradient-tile
-    spectra if the caller already has them (`grad_spectra`)."""
-    lib = _lib.load()
-    nimg, Cout, OH, OW = dy.shape
-    Cin = bank.shape[1]
-    dev = dy.device
-    if G is None:
-        G = grad_spectra(dy)
-    B2 = spectra_for(bank.detach().permute(1, 0, 2, 3).contiguous(), correlate=False)         # spectra of (Cin, Cout, 5, 5)
-    st = torch.cuda.current_stream().cuda_stream
-    H, W = OH + 4, OW + 4
-    dx = torch.empty((nimg, Cin, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-    with torch.cuda.device(dev):
-        Cg = contract(G, B2, G.shape[1])                                          # (F, M, 2 Cin)
-        T2 = torch.empty(max(lib.eqa_fft48k5_workspace_bytes(nimg, N * tiles(H), OW, Cin), 4) // 4, dtype=torch.float32, device=dev)
-        _lib.check(lib.eqa_fft48k5_input_grad(Cg.data_ptr(), T2.data_ptr(), dx.data_ptr(), nimg, H, W, Cin, st), "eqa_fft48k5_input_grad")
-    return dx
-
-
-def grad_spectra(dy: torch.Tensor) -> torch.Tensor:
-    """Spectra of the disjoint 44 x 44 tiles of an output gradient (channels-last), (F, M, 2 Cout): shared by the filter
-    gradient and the input gradient."""
-    lib = _lib.load()
-    nimg, Cout, OH, OW = dy.shape
-    M = nimg * tiles(OH + 4) * tiles(OW + 4)
-    T = torch.empty(max(lib.eqa_fft48k5_workspace_bytes(nimg, OH, OW, Cout), 4) // 4, dtype=torch.float32, device=dy.device)
-    G = spectra_buffer(M, 2 * Cout, dy.device)
-    with torch.cuda.device(dy.device):
-        _lib.check(lib.eqa_fft48k5_grad_transform(dy.data_ptr(), T.data_ptr(), G.data_ptr(), nimg, OH, OW, Cout,
-                                                  torch.cuda.current_stream().cuda_stream), "eqa_fft48k5_grad_transform")
-    return G
-
-
 # ----------------------------------------------------------------------------------------------------------------------------------
 # Kernel sizes other than 5 (round 4): the same scheme with O = 49 - k outputs per tile, through eqa_fft48_* (two-pass kernels).
 # The reference's kernel_size is a free constructor argument (escnn_networks.py:19-44): its tutorial trains k = 9, its test k = 3.
-# k = 5 keeps the functions above (fused / pipelined transforms).
+# k = 5 keeps kernels of its own (eqa_fft48k5_*: fused / pipelined transforms, the window-sum / statistics epilogues, the grouped and
+# fused-lifting inputs).  The transforms of the two families take the same arguments but for k, which `_transform` / `_workspace` add.
 # ----------------------------------------------------------------------------------------------------------------------------------
 KSIZES = (3, 5, 7, 9)
 
 
-def tiles_k(n: int, k: int) -> int:
-    o = N + 1 - k
-    return 0 if n < k else (n - (k - 1) + o - 1) // o
+def _transform(name: str, k: int, *args) -> None:
+    """Launch eqa_fft48k5_<name>(*args) for k = 5, eqa_fft48_<name>(..., k, stream) otherwise (args end with the stream)."""
+    lib = _lib.load()
+    if k == 5:
+        _lib.check(getattr(lib, "eqa_fft48k5_" + name)(*args), "eqa_fft48k5_" + name)
+    else:
+        _lib.check(getattr(lib, "eqa_fft48_" + name)(*args[:-1], k, args[-1]), "eqa_fft48_" + name)
+
+
+def _workspace(k: int, nimg: int, rows: int, out_cols: int, C: int, device) -> torch.Tensor:
+    """The scratch buffer a transform over (nimg, rows, out_cols, C) asks for."""
+    lib = _lib.load()
+    nbytes = lib.eqa_fft48k5_workspace_bytes(nimg, rows, out_cols, C) if k == 5 else lib.eqa_fft48_workspace_bytes(nimg, rows, out_cols, C, k)
+    return torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=device)
 
 
 def applicable_k(x_shape, cin: int, cout: int, k: int, device, channels_last: bool = True) -> bool:
@@ -539,7 +464,7 @@ def spectra_for_k(bank: torch.Tensor, correlate: bool = True):
     lib = _lib.load()
     Cout, Cin = bank.shape[:2]
     assert bank.is_cuda and bank.dtype == torch.float32 and bank.shape[-2] == k and lib.eqa_fft48_supported(k)
-    st = torch.cuda.current_stream().cuda_stream
+    st = ops._stream()
     with torch.cuda.device(bank.device):
         if gemm3m_supported(Cin, Cout):
             B3 = torch.empty(lib.eqa_fft48k5_spectra3m_floats(Cin, Cout), dtype=torch.float32, device=bank.device)
@@ -553,94 +478,147 @@ def spectra_for_k(bank: torch.Tensor, correlate: bool = True):
 
 
 def conv_kxk(x: torch.Tensor, B, k: int, bias: Optional[torch.Tensor], relu: bool, in_bias: Optional[torch.Tensor] = None,
-             in_relu: bool = False, keep_V: Optional[list] = None) -> torch.Tensor:
-    """`conv5x5` for any supported k (no window-sum / statistics epilogues off k = 5): channels-last (nimg, Cin, H, W) ->
-    channels-last (nimg, Cout, H-k+1, W-k+1) = [relu](conv2d(act(x), g) + bias), B = spectra_for_k(g)."""
-    if k == 5:
-        return conv5x5(x, B, bias, relu, in_bias, in_relu, keep_V=keep_V)
+             in_relu: bool = False, keep_V: Optional[list] = None, sums_k: int = 0, stats: Optional[list] = None) -> torch.Tensor:
+    """x: channels-last (nimg,Cin,H,W) -> channels-last (nimg,Cout,H-k+1,W-k+1) = [relu](conv2d(act(x), g) + bias) with
+    B = spectra_for_k(g) (either form) and act(x) = [relu](x + in_bias[c]) applied while loading.
+    ``keep_V``: a list that receives the input spectra V (training: the filter gradient reuses them).
+    k = 5 only (`conv5x5`): x may be a `GroupedMap` or a `LiftedInput`; ``sums_k`` > 0: return instead the (nimg, Cout, sums_k, sums_k)
+    fp64 window sums of that output (the linearised last layer consumes only those); ``stats``: a list that receives the
+    (rows, Cout, 2) fp64 partial sums of the output's per-channel sum / sum of squares, taken by the inverse transform (training,
+    no bias / activation; the caller checks ``output_stats_supported``)."""
     lib = _lib.load()
     nimg, Cin, H, W = x.shape
-    Cout = B.cout if isinstance(B, Spectra3M) else B.shape[2] // 2
+    if isinstance(B, Spectra3M):
+        Cout = B.cout
+        assert B.cin == Cin
+    else:
+        Cout = B.shape[2] // 2
+        assert B.shape == (F, 2 * Cin, 2 * Cout)
+    assert k == 5 or not (sums_k or stats is not None or isinstance(x, (GroupedMap, LiftedInput))), "k = 5 only"
     OH, OW = H - k + 1, W - k + 1
-    M = nimg * tiles_k(H, k) * tiles_k(W, k)
+    TX = tiles_k(W, k)
+    M = nimg * tiles_k(H, k) * TX
     dev = x.device
-    st = torch.cuda.current_stream().cuda_stream
-    T = torch.empty(max(lib.eqa_fft48_workspace_bytes(nimg, H, OW, Cin, k), 4) // 4, dtype=torch.float32, device=dev)
+    st = ops._stream()
     V = spectra_buffer(M, 2 * Cin, dev)
+    p_bias = bias.data_ptr() if bias is not None else None
+    vbound = None
     with torch.cuda.device(dev):
-        with _timed("fft_input"):
-            _lib.check(lib.eqa_fft48_input(x.data_ptr(), T.data_ptr(), V.data_ptr(), in_bias.data_ptr() if in_bias is not None else None,
-                                           int(in_relu), nimg, H, W, Cin, k, st), "eqa_fft48_input")
-        del T
+        if isinstance(x, LiftedInput):
+            assert in_bias is None and not in_relu
+            with _timed("lift_fft_input"):
+                vbound = x.spectra_into(V, B, st)
+        else:
+            T = _workspace(k, nimg, H, OW, Cin, dev)
+            with _timed("fft_input"):
+                _transform("input_grouped" if isinstance(x, GroupedMap) else "input", k, x.data_ptr(), T.data_ptr(), V.data_ptr(),
+                           in_bias.data_ptr() if in_bias is not None else None, int(in_relu), nimg, H, W, Cin, st)
+            del T
         with _timed("fft_gemm"):
-            Mo = contract(V, B, M)
+            Mo = contract(V, B, M, vbound)
         if keep_V is not None:
             keep_V.append(V)
         del V
-        T2 = torch.empty(max(lib.eqa_fft48_workspace_bytes(nimg, OH, OW, Cout, k), 4) // 4, dtype=torch.float32, device=dev)
+        T2 = _workspace(k, nimg, OH, OW, Cout, dev)
+        if sums_k:
+            S = torch.empty((nimg, Cout, sums_k, sums_k), dtype=torch.float64, device=dev)
+            ws = torch.empty(nimg * OH * TX * Cout * (2 * sums_k - 1), dtype=torch.float32, device=dev)
+            with _timed("fft_output_sums"):
+                _lib.check(lib.eqa_fft48k5_output_sums(Mo.data_ptr(), T2.data_ptr(), p_bias, int(relu), S.data_ptr(), ws.data_ptr(),
+                                                       nimg, OH, OW, Cout, sums_k, st), "eqa_fft48k5_output_sums")
+            return S
         y = torch.empty((nimg, Cout, OH, OW), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        if stats is not None:
+            assert bias is None and not relu
+            part = torch.empty((lib.eqa_fft48k5_output_stats_rows(nimg, OH, OW, Cout), Cout, 2), dtype=torch.float64, device=dev)
+            with _timed("fft_output"):
+                _lib.check(lib.eqa_fft48k5_output_stats(Mo.data_ptr(), T2.data_ptr(), y.data_ptr(), part.data_ptr(), nimg, OH, OW, Cout, st),
+                           "eqa_fft48k5_output_stats")
+            stats.append(part)
+            return y
         with _timed("fft_output"):
-            _lib.check(lib.eqa_fft48_output(Mo.data_ptr(), T2.data_ptr(), bias.data_ptr() if bias is not None else None, int(relu),
-                                            y.data_ptr(), nimg, OH, OW, Cout, k, st), "eqa_fft48_output")
-    return y
+            _transform("output", k, Mo.data_ptr(), T2.data_ptr(), p_bias, int(relu), y.data_ptr(), nimg, OH, OW, Cout, st)
+        return y
 
 
-def grad_spectra_k(dy: torch.Tensor, k: int) -> torch.Tensor:
-    if k == 5:
-        return grad_spectra(dy)
-    lib = _lib.load()
+def conv5x5(x: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor], relu: bool,
+            in_bias: Optional[torch.Tensor] = None, in_relu: bool = False, sums_k: int = 0,
+            keep_V: Optional[list] = None, stats: Optional[list] = None) -> torch.Tensor:
+    """`conv_kxk` at k = 5, B = spectra_for(g): channels-last (nimg,Cin,H,W), a `GroupedMap` or a `LiftedInput` -> channels-last
+    (nimg,Cout,H-4,W-4), or its window sums (``sums_k``), or the map and its batch-norm statistics (``stats``)."""
+    return conv_kxk(x, B, 5, bias, relu, in_bias, in_relu, keep_V, sums_k, stats)
+
+
+def grad_spectra(dy: torch.Tensor, k: int = 5) -> torch.Tensor:
+    """Spectra of the disjoint (49 - k) x (49 - k) tiles of an output gradient (channels-last), (F, M, 2 Cout): shared by the filter
+    gradient and the input gradient."""
     nimg, Cout, OH, OW = dy.shape
     M = nimg * tiles_k(OH + k - 1, k) * tiles_k(OW + k - 1, k)
-    T = torch.empty(max(lib.eqa_fft48_workspace_bytes(nimg, OH, OW, Cout, k), 4) // 4, dtype=torch.float32, device=dy.device)
+    T = _workspace(k, nimg, OH, OW, Cout, dy.device)
     G = spectra_buffer(M, 2 * Cout, dy.device)
     with torch.cuda.device(dy.device):
-        _lib.check(lib.eqa_fft48_grad_transform(dy.data_ptr(), T.data_ptr(), G.data_ptr(), nimg, OH, OW, Cout, k,
-                                                torch.cuda.current_stream().cuda_stream), "eqa_fft48_grad_transform")
+        _transform("grad_transform", k, dy.data_ptr(), T.data_ptr(), G.data_ptr(), nimg, OH, OW, Cout, ops._stream())
     return G
 
 
 def filter_grad_k(V: torch.Tensor, dy: torch.Tensor, cin: int, k: int, G: Optional[torch.Tensor] = None) -> torch.Tensor:
-    if k == 5:
-        return filter_grad(V, dy, cin, G)
+    """d loss / d filter bank (Cout, Cin, k, k) of y = conv2d(x, bank) from V = the spectra of x's tiles (``keep_V`` of the
+    forward pass) and the output gradient dy (channels-last): spectra of the disjoint gradient tiles, one batched GEMM
+    over the tiles per frequency (D[f] = V[f]^T G[f]), and the inverse transform restricted to the k x k support
+    (eqa_fft48k5_grad_transform / _filter_grad).  2.5 multiplies per output at k = 5 as in the forward pass; Winograd's filter
+    gradient (`winograd.filter_grad`) needs 4 and a 4x larger transformed gradient."""
     lib = _lib.load()
     nimg, Cout, OH, OW = dy.shape
     dev = dy.device
     M = V.shape[1]
     assert V.shape == (F, M, 2 * cin) and M == nimg * tiles_k(OH + k - 1, k) * tiles_k(OW + k - 1, k)
-    st = torch.cuda.current_stream().cuda_stream
+    st = ops._stream()
     if G is None:
-        G = grad_spectra_k(dy, k)
+        G = grad_spectra(dy, k)
     dbank = torch.empty((Cout, cin, k, k), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        if GEMM == "3m" and lib.eqa_fft48k5_wgrad3m_supported(cin, Cout) and os.environ.get("EQA_FFT_WGRAD3M", "1") != "0":
-            D = torch.empty((F, cin, 2, Cout), dtype=torch.float32, device=dev)
+        packed = GEMM == "3m" and lib.eqa_fft48k5_wgrad3m_supported(cin, Cout) and os.environ.get("EQA_FFT_WGRAD3M", "1") != "0"
+        if packed:
+            # the contraction over the tiles in the 3-multiplication form on the fp32 MFMA (the library's real GEMM: 4 products)
+            D = torch.empty((F, cin, 2, Cout), dtype=torch.float32, device=dev)      # Dr | Di per input channel
             _lib.check(lib.eqa_fft48k5_wgrad3m(V.data_ptr(), G.data_ptr(), D.data_ptr(), M, cin, Cout, st), "eqa_fft48k5_wgrad3m")
-            _lib.check(lib.eqa_fft48_filter_grad(D.data_ptr(), dbank.data_ptr(), Cout, cin, k, 1, st), "eqa_fft48_filter_grad")
-            return dbank
-        D = torch.bmm(V.transpose(1, 2), G)
-        _lib.check(lib.eqa_fft48_filter_grad(D.data_ptr(), dbank.data_ptr(), Cout, cin, k, 0, st), "eqa_fft48_filter_grad")
+        else:
+            D = torch.bmm(V.transpose(1, 2), G)                   # (F, 2 Cin, 2 Cout)
+        if k != 5:                                                # (one entry point, told which D it reads)
+            _lib.check(lib.eqa_fft48_filter_grad(D.data_ptr(), dbank.data_ptr(), Cout, cin, k, int(packed), st), "eqa_fft48_filter_grad")
+        elif packed:
+            _lib.check(lib.eqa_fft48k5_filter_grad3m(D.data_ptr(), dbank.data_ptr(), Cout, cin, st), "eqa_fft48k5_filter_grad3m")
+        else:
+            _lib.check(lib.eqa_fft48k5_filter_grad(D.data_ptr(), dbank.data_ptr(), Cout, cin, st), "eqa_fft48k5_filter_grad")
     return dbank
 
 
-def input_grad_k(dy: torch.Tensor, bank: torch.Tensor, G: Optional[torch.Tensor] = None) -> torch.Tensor:
+def filter_grad(V: torch.Tensor, dy: torch.Tensor, cin: int, G: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return filter_grad_k(V, dy, cin, 5, G)
+
+
+def input_grad(dy: torch.Tensor, bank: torch.Tensor, G: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d loss / d x (channels-last (nimg, Cin, OH+k-1, OW+k-1)) of y = conv2d(x, bank): the full convolution of dy with the
+    filters, tile by tile in the frequency domain with overlap-add (eqa_fft48k5_input_grad).  ``G``: the gradient-tile
+    spectra if the caller already has them (`grad_spectra`)."""
     k = bank.shape[-1]
-    if k == 5:
-        return input_grad(dy, bank, G)
-    lib = _lib.load()
     nimg, Cout, OH, OW = dy.shape
     Cin = bank.shape[1]
     dev = dy.device
     if G is None:
-        G = grad_spectra_k(dy, k)
-    B2 = spectra_for_k(bank.detach().permute(1, 0, 2, 3).contiguous(), correlate=False)
-    st = torch.cuda.current_stream().cuda_stream
+        G = grad_spectra(dy, k)
+    B2 = spectra_for_k(bank.detach().permute(1, 0, 2, 3).contiguous(), correlate=False)       # spectra of (Cin, Cout, k, k)
+    st = ops._stream()
     H, W = OH + k - 1, OW + k - 1
     dx = torch.empty((nimg, Cin, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
     with torch.cuda.device(dev):
-        Cg = contract(G, B2, G.shape[1])
-        T2 = torch.empty(max(lib.eqa_fft48_workspace_bytes(nimg, N * tiles_k(H, k), OW, Cin, k), 4) // 4, dtype=torch.float32, device=dev)
-        _lib.check(lib.eqa_fft48_input_grad(Cg.data_ptr(), T2.data_ptr(), dx.data_ptr(), nimg, H, W, Cin, k, st), "eqa_fft48_input_grad")
+        Cg = contract(G, B2, G.shape[1])                                          # (F, M, 2 Cin)
+        T2 = _workspace(k, nimg, N * tiles_k(H, k), OW, Cin, dev)
+        _transform("input_grad", k, Cg.data_ptr(), T2.data_ptr(), dx.data_ptr(), nimg, H, W, Cin, st)
     return dx
+
+
+grad_spectra_k, input_grad_k = grad_spectra, input_grad
 
 
 class ConvKxKFunction(torch.autograd.Function):

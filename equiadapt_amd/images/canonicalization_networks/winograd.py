@@ -143,7 +143,7 @@ def filter_grad(x: torch.Tensor, dY: torch.Tensor, m: int, V_saved: Optional[tor
     V = V_saved if have_V else torch.empty((chunk * TY * TX, P, Cin), dtype=torch.float32, device=x.device)
     dM = torch.empty((chunk * TY * TX, P, Cout), dtype=torch.float32, device=x.device)
     dU = torch.zeros((P, Cin, Cout), dtype=torch.float32, device=x.device)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = ops._stream()
     with torch.cuda.device(x.device):
         for b0 in range(0, B, chunk):
             nimg = min(chunk, B - b0)
@@ -241,7 +241,7 @@ def conv5x5(x: torch.Tensor, U: torch.Tensor, bias: Optional[torch.Tensor], relu
         y = None
     else:
         y = torch.empty((B, Cout, OH, OW), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = ops._stream()
     chunk = min(CHUNK_IMAGES * (m * m // 4), B)       # same V / M footprint per chunk for both tile sizes
     V = torch.empty((chunk * TY * TX, P, Cin), dtype=torch.float32, device=x.device)
     M = torch.empty((chunk * TY * TX, P, Cout), dtype=torch.float32, device=x.device)

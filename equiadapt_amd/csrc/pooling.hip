@@ -1,4 +1,4 @@
-// libeqa_hip.so, part 2 of 5 -- reductions of the canonicalization network's feature map: group pooling + argmax (I3, I4),
+// libeqa_hip.so, part 2 of 7 -- reductions of the canonicalization network's feature map: group pooling + argmax (I3, I4),
 // window sums of the linearised last convolution (NCHW and channels-last), their GEMV, bias + ReLU.  C ABI: include/eqa_hip.h.
 #include "eqa_common.hpp"
 

@@ -19,8 +19,8 @@
 //               a wave's B loads are contiguous 1 KB runs
 // and MFMA step (b, t) multiplies the k-pair {16 s + 8 b + t, 16 s + 8 b + 4 + t}.
 // Epilogue.  Stored straight from the accumulator layout a tile is 64 eight-byte stores per lane, and the CU's store path takes
-// ~90 cycles per such instruction: 23 k cycles per tile during which the wave's matrix pipe idles (measured with
-// tools/micro/cgemm3m_bench.hip: 4.08 ms with, 3.46 ms without the stores).  So a finished tile is only COMBINED
+// ~90 cycles per such instruction: 23 k cycles per tile during which the wave's matrix pipe idles (4.08 ms with, 3.46 ms without
+// the stores: HISTORY.md 3.4, profiles/r02/README.md).  So a finished tile is only COMBINED
 // (Cr = T1 - T2, Ci = T3 - T1 - T2) and parked in the wave's private 32 KB of LDS (64 ds_write_b64, ~1.5 k cycles); it leaves
 // for HBM during the NEXT tile's MFMA stream, two whole 512-byte rows per ds_read_b128 + global_store_dwordx4 pair, 32 / S pairs
 // per K-stage -- LDS and store instructions issue in the shadow of the 64-cycle MFMAs.
@@ -36,52 +36,28 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "cgemm3m_common.inc"   // the wave-tile walk, the buffer descriptors, the parked tile: shared with cgemm3m_bf16.hip
 
-#ifdef EQA_CGEMM_CLOCK   // experiment (tools/micro/cgemm3m_bench.hip): shader-cycle stamps per wave [total, stage loops, epilogues, tiles]
-__device__ unsigned long long g_cg_clock[1024 * 4];
-#define CG_STAMP(x) const unsigned long long x = __builtin_readcyclecounter()
-#else
-#define CG_STAMP(x)
-#endif
-
-constexpr int kTileM = 64, kTileN = 64;   // wave tile: rows (tiles of the FFT convolution) x complex output channels
-constexpr int kStageK = 16;               // complex k per stage = one [Re x 16 | Im x 16] group of V
+constexpr unsigned kBTileBytes = 3 * 2 * 64 * 4 * 4;   // B3 per (K-stage, 32-column tile): [part r/i/s][b] fragments of 1 KB
 
 struct OperandSet {                       // one K-stage of MFMA operands: 80 registers
   f32x4 ar[2][2], ai[2][2];               // [m][b]
   f32x4 b[3][2][2];                       // [part r/i/s][n][b]
 };
 
-// Operand loads go through buffer descriptors: a wave-uniform descriptor (rebuilt per tile by scalar code) + a scalar byte offset
-// (frequency / K-stage, advanced by scalar adds) + a 32-bit lane offset that is constant within a tile.  No vector address
-// arithmetic in the MFMA stream (a VALU instruction there costs ~6 MFMA cycles), and rows beyond the buffer read as zero instead
-// of needing a clamp.
-struct StageAddr {
-  __amdgpu_buffer_rsrc_t a, b;   // rows of V the tile reads; B3[f]
-  unsigned sa, sb;               // scalar byte offsets of the stage
-};
-
-__device__ __forceinline__ f32x4 buf_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
 // aoff0 / aoff1: byte offset of this lane's row (the two 32-row subtiles) + 16 h; boff = 16 * lane.  A row's stage is one
 // [Re x 16 | Im x 16] piece: k-block b at +32 b, Im at +64.  In the order the MFMAs consume them: all of b = 0, then b = 1.
 __device__ __forceinline__ void load_stage(OperandSet& o, const StageAddr& at, unsigned aoff0, unsigned aoff1, unsigned boff) {
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
-    o.ar[0][b] = buf_ld(at.a, aoff0 + 32 * b, at.sa);
-    o.ai[0][b] = buf_ld(at.a, aoff0 + 32 * b + 64, at.sa);
-    o.ar[1][b] = buf_ld(at.a, aoff1 + 32 * b, at.sa);
-    o.ai[1][b] = buf_ld(at.a, aoff1 + 32 * b + 64, at.sa);
+    o.ar[0][b] = buf_ld<f32x4>(at.a, aoff0 + 32 * b, at.sa);
+    o.ai[0][b] = buf_ld<f32x4>(at.a, aoff0 + 32 * b + 64, at.sa);
+    o.ar[1][b] = buf_ld<f32x4>(at.a, aoff1 + 32 * b, at.sa);
+    o.ai[1][b] = buf_ld<f32x4>(at.a, aoff1 + 32 * b + 64, at.sa);
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) o.b[p][n][b] = buf_ld(at.b, boff + ((n * 3 + p) * 2 + b) * 1024, at.sb);
+      for (int p = 0; p < 3; ++p) o.b[p][n][b] = buf_ld<f32x4>(at.b, boff + ((n * 3 + p) * 2 + b) * 1024, at.sb);
   }
 }
 
@@ -110,30 +86,6 @@ __device__ __forceinline__ void mma_stage(const OperandSet& o, f32x16 (&acc)[3][
   }
 }
 
-constexpr int kLdsRowFloats = 2 * kTileN;                 // one parked row: 64 complex = 128 floats = 512 bytes
-constexpr int kLdsWaveFloats = kTileM * kLdsRowFloats;    // 32 KB per wave
-
-// Where a parked tile goes: a buffer over the tile's rows that lie inside M (rows beyond it fall outside num_records and are
-// dropped by the hardware: no branch), the lane's byte offset for row pair 0, the step to the next pair, a scalar offset.
-struct ParkedDst {
-  __amdgpu_buffer_rsrc_t rsrc;
-  int voff, pair_bytes;
-  unsigned soff;
-};
-
-__device__ __forceinline__ void store_pair(const ParkedDst& d, int p, f32x4 v) {
-#ifdef EQA_CGEMM_NOSTORE      // experiment: no global stores (the value stays live through the asm)
-  asm volatile("" ::"v"(v));
-#else
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), d.rsrc, d.voff + p * d.pair_bytes, d.soff, 0);
-#endif
-}
-
-// row pairs [p0, p1) of the parked tile -> Mo: lanes 0..31 carry row 2p, lanes 32..63 row 2p + 1, 16 bytes each
-__device__ __forceinline__ void flush_rows(const float* lds_lane, const ParkedDst& d, int p0, int p1) {
-  for (int p = p0; p < p1; ++p) store_pair(d, p, *reinterpret_cast<const f32x4*>(lds_lane + p * (2 * kLdsRowFloats)));
-}
-
 // One K-stage: request the next stage's operands, send NPAIR row pairs of the parked tile on their way, 96 MFMAs -- as ONE
 // scheduling region whose instruction order is then pinned: the LDS reads first, one global load behind every third MFMA (a run of
 // 20 loads would stall the in-order wave for ~300 cycles with the matrix pipe drained), the stores further down.
@@ -148,7 +100,6 @@ __device__ __forceinline__ void run_stage(OperandSet& nxt, const OperandSet& cur
   mma_stage<FIRST>(cur, acc);
 #pragma unroll
   for (int k = 0; k < NPAIR; ++k) store_pair(dst, p0 + k, park[k]);
-#ifndef EQA_CGEMM_NOPIN
   __builtin_amdgcn_sched_group_barrier(0x100, NPAIR, 0);            // DS reads
 #pragma unroll
   for (int k = 0; k < 20; ++k) {
@@ -161,7 +112,6 @@ __device__ __forceinline__ void run_stage(OperandSet& nxt, const OperandSet& cur
     __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);              // 1 global store
   }
   __builtin_amdgcn_sched_group_barrier(0x008, 36 - 2 * NPAIR, 0);
-#endif
 }
 
 // V (F, pitch, 2 Cin) rows [Re x 16 | Im x 16] per 16 channels; B3 (F, S, Cout/32, 3, 2, 64, 4); Mo (F, pitch, 2 Cout) interleaved
@@ -183,62 +133,23 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_kernel(const float* __rest
   __shared__ __attribute__((aligned(16))) float lds_all[4 * kLdsWaveFloats];
   float* lds_w = lds_all + wave * kLdsWaveFloats;       // this wave's parking space for one finished tile
   const float* lds_lane = lds_w + h * kLdsRowFloats + i * 4;
-  const size_t rowf = (size_t)2 * Cin, mo_row = (size_t)2 * Cout;           // floats per row of V / Mo
-  const unsigned b_stage_bytes = (unsigned)(Cout / 32) * 3 * 2 * 64 * 4 * 4;                    // bytes per (f, stage) of B3
-  const unsigned a_stage = 32u * 4u;                                        // bytes from one K-stage of a row to the next
+  const WaveTileWalk<float, kBTileBytes> walk(V, B3, Mo, M, pitch, Cin, Cout, xcd, wpf, n_ct, S, i, h);
   const unsigned boff = lane * 16;
-
-  // a wave-tile u (index in this XCD's sequence): operand descriptors + scalar offsets at stage 0, the lane's row offsets, its
-  // coordinates.  All sizes are < 2^32 bytes (host-checked).
-  auto locate = [&](int u, StageAddr& at, unsigned& aoff0, unsigned& aoff1, int& f, int& row0, int& ct) {
-#ifdef EQA_CGEMM_SAMETILE     // experiment (tools/micro/cgemm3m_bench.hip): every wave-tile reads tile 0 -- operands always cached
-    u = 0;
-#endif
-    const int fi = u / wpf, r = u - fi * wpf;
-    f = xcd + kXcd * fi;
-    const int rt = r / n_ct;
-    ct = r - rt * n_ct;
-    row0 = rt * kTileM;
-    at.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V) + (size_t)f * pitch * rowf, 0, (unsigned)((size_t)pitch * rowf * 4), 0x00020000);
-    at.sa = 0;
-    aoff0 = (unsigned)((size_t)(row0 + i) * rowf + 4 * h) * 4u;        // rows >= pitch fall outside the descriptor and read as 0
-    aoff1 = aoff0 + 32 * (unsigned)rowf * 4u;
-    at.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B3) + (size_t)f * S * (b_stage_bytes / 4), 0, (unsigned)S * b_stage_bytes, 0x00020000);
-    at.sb = (unsigned)(2 * ct) * (3 * 2 * 64 * 4 * 4);
-  };
-  auto at_stage = [&](const StageAddr& t, int s) { return StageAddr{t.a, t.b, t.sa + s * a_stage, t.sb + s * b_stage_bytes}; };
-  // destination of the tile (f, row0, ct) once it is parked
-  auto parked = [&](int f, int row0, int ct) {
-    const int rows = min(kTileM, M - row0);
-    ParkedDst d;
-    d.rsrc = __builtin_amdgcn_make_buffer_rsrc(Mo + ((size_t)f * pitch + row0) * mo_row, 0, (unsigned)(rows * mo_row * 4), 0x00020000);
-    d.voff = (h * (int)mo_row + ct * kLdsRowFloats + i * 4) * 4;
-    d.pair_bytes = 2 * (int)mo_row * 4;
-    d.soff = 0;
-    return d;
-  };
 
   StageAddr at;
   unsigned aoff0, aoff1;
   int f, row0, ct;
-  locate(q, at, aoff0, aoff1, f, row0, ct);
-  ParkedDst dst = parked(f, row0, ct);
-  dst.rsrc = __builtin_amdgcn_make_buffer_rsrc(Mo, 0, 0, 0x00020000);       // nothing parked yet: an empty buffer drops the stores
+  walk.locate(q, at, aoff0, aoff1, f, row0, ct);
+  ParkedDst dst = walk.nothing_parked(f, row0, ct);
   OperandSet s0, s1;
-  CG_STAMP(c_begin);
-#ifdef EQA_CGEMM_CLOCK
-  unsigned long long c_mma = 0, c_epi = 0, c_tiles = 0;
-#endif
   load_stage(s0, at, aoff0, aoff1, boff);
   for (int u = q; u < total; u += waves_per_xcd) {
-    CG_STAMP(c0);
     f32x16 acc[3][2][2];      // never cleared: the first stage's products start from zero (mma_stage<true>)
     // the tile after this one (or this one again when it is the last: a harmless reload instead of a conditional load)
-    const int un = u + waves_per_xcd < total ? u + waves_per_xcd : u;
     StageAddr nat;
     unsigned naoff0, naoff1;
     int nf, nrow0, nct;
-    locate(un, nat, naoff0, naoff1, nf, nrow0, nct);
+    walk.locate(u + waves_per_xcd < total ? u + waves_per_xcd : u, nat, naoff0, naoff1, nf, nrow0, nct);
     // two K-stages; the scheduling barriers keep the next stage's loads INSIDE this stage's MFMA stream: left alone, the compiler
     // sinks them to their first use (the next stage) to save registers and every stage starts with an exposed HBM round trip
     auto stage_pair = [&](int s, auto first_tag) {
@@ -246,18 +157,18 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_kernel(const float* __rest
       const bool more = s + 2 < S;
       if (NPAIR > 0) {
         __builtin_amdgcn_sched_barrier(0);
-        run_stage<NPAIR, kFirst>(s1, s0, acc, at_stage(at, s + 1), aoff0, aoff1, boff, lds_lane, dst, s * NPAIR);
+        run_stage<NPAIR, kFirst>(s1, s0, acc, walk.at_stage(at, s + 1), aoff0, aoff1, boff, lds_lane, dst, s * NPAIR);
         __builtin_amdgcn_sched_barrier(0);
-        run_stage<NPAIR>(s0, s1, acc, more ? at_stage(at, s + 2) : nat, more ? aoff0 : naoff0, more ? aoff1 : naoff1, boff, lds_lane, dst,
-                         (s + 1) * NPAIR);
+        run_stage<NPAIR>(s0, s1, acc, more ? walk.at_stage(at, s + 2) : nat, more ? aoff0 : naoff0, more ? aoff1 : naoff1, boff,
+                         lds_lane, dst, (s + 1) * NPAIR);
         __builtin_amdgcn_sched_barrier(0);
       } else {
-        load_stage(s1, at_stage(at, s + 1), aoff0, aoff1, boff);
+        load_stage(s1, walk.at_stage(at, s + 1), aoff0, aoff1, boff);
         flush_rows(lds_lane, dst, (32 * s) / S, (32 * (s + 1)) / S);
         __builtin_amdgcn_sched_barrier(0);
         mma_stage<kFirst>(s0, acc);
         __builtin_amdgcn_sched_barrier(0);
-        load_stage(s0, more ? at_stage(at, s + 2) : nat, more ? aoff0 : naoff0, more ? aoff1 : naoff1, boff);
+        load_stage(s0, more ? walk.at_stage(at, s + 2) : nat, more ? aoff0 : naoff0, more ? aoff1 : naoff1, boff);
         flush_rows(lds_lane, dst, (32 * (s + 1)) / S, (32 * (s + 2)) / S);
         __builtin_amdgcn_sched_barrier(0);
         mma_stage(s1, acc);
@@ -266,38 +177,11 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_kernel(const float* __rest
     };
     stage_pair(0, std::true_type{});
     for (int s = 2; s < S; s += 2) stage_pair(s, std::false_type{});
-    CG_STAMP(c1);
-    // epilogue: Cr = T1 - T2, Ci = T3 - T1 - T2 into the wave's LDS tile [row][complex column]; accumulator register e of lane
-    // (h, j) is row (e & 3) + 8 (e >> 2) + 4 h, column j of its 32 x 32 block.  (All of the previous tile's rows have left the
-    // LDS: the stage loop above flushed its 32 row pairs; LDS operations of one wave execute in order.)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int r = 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-          const float t1 = acc[0][m][n][e], t2 = acc[1][m][n][e], t3 = acc[2][m][n][e];
-          f32x2v c;
-          c[0] = t1 - t2;
-          c[1] = t3 - t1 - t2;
-          *reinterpret_cast<f32x2v*>(lds_w + r * kLdsRowFloats + (32 * n + i) * 2) = c;
-        }
-      }
-    dst = parked(f, row0, ct);
+    park_tile(acc, lds_w, i, h);
+    dst = walk.parked(f, row0, ct);
     at = nat; aoff0 = naoff0; aoff1 = naoff1; f = nf; row0 = nrow0; ct = nct;
-#ifdef EQA_CGEMM_CLOCK
-    CG_STAMP(c2);
-    c_mma += c1 - c0; c_epi += c2 - c1; ++c_tiles;
-#endif
   }
   flush_rows(lds_lane, dst, 0, 32);       // the wave's last tile
-#ifdef EQA_CGEMM_CLOCK
-  if (lane == 0) {
-    unsigned long long* o = g_cg_clock + (size_t)(blockIdx.x * 4 + wave) * 4;
-    o[0] = __builtin_readcyclecounter() - c_begin; o[1] = c_mma; o[2] = c_epi; o[3] = c_tiles;
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -385,14 +269,9 @@ __global__ __launch_bounds__(256, 1) void fft_wgrad3m_kernel(const float* __rest
     const int fi = u / wpf, r = u - fi * wpf;
     const int f = xcd + kXcd * fi;
     const int it = r / n_ot, ot = r - it * n_ot;
-#ifdef EQA_WG_SAMEF   // experiment: every wave tile reads frequency 0 -- operands always cached
-    const int fl = 0;
-#else
-    const int fl = f;
-#endif
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V) + (size_t)fl * pitch * rowa, 0,
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V) + (size_t)f * pitch * rowa, 0,
                                                                         (unsigned)((size_t)M * rowa * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G) + (size_t)fl * pitch * rowb, 0,
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G) + (size_t)f * pitch * rowb, 0,
                                                                         (unsigned)((size_t)M * rowb * 4), 0x00020000);
     // this lane's 2 channels of tile row h: group i / 8 of the wave tile's four [Re x 16 | Im x 16] groups, floats 2 (i % 8) ..
     const unsigned aoff = (unsigned)((size_t)h * rowa + (size_t)it * 128 + (i >> 3) * 32 + (i & 7) * 2) * 4u;
@@ -453,21 +332,15 @@ int64_t eqa_fft48k5_spectra3m_floats(int Cin, int Cout) {
 }
 
 int eqa_fft48k5_cgemm3m(const float* V, const float* B3, float* Mo, int64_t M, int Cin, int Cout, void* stream) {
-  if (!V || !B3 || !Mo || M < 0 || Cin <= 0 || Cout <= 0) return EQA_ERR_INVALID_ARG;
-  if (M == 0) return EQA_OK;
+  const int st = check_contraction_args(V, B3, Mo, M, Cin, Cout);
+  if (st != EQA_OK) return st == kNothingToDo ? EQA_OK : st;
+  if ((int64_t)Cin * Cout * 3 * 4 > 0x7fffffffLL) return EQA_ERR_UNSUPPORTED;      // one frequency of B3: a descriptor range
   const int F = eqa_fft48k5_frequencies();
-  // every descriptor range and lane offset must fit 32 bits: one frequency of V / Mo, one frequency of B3
-  const int64_t fm_bytes = ((M | 1) + 64) * 2 * (int64_t)std::max(Cin, Cout) * 4;
-  if (!eqa_fft48k5_cgemm3m_supported(Cin, Cout) || M > 0x3fffff || fm_bytes > 0x7fffffffLL || (int64_t)Cin * Cout * 3 * 4 > 0x7fffffffLL ||
-      (((uintptr_t)V | (uintptr_t)B3 | (uintptr_t)Mo) & 15))
-    return EQA_ERR_UNSUPPORTED;
   const int n_rt = (int)((M + kTileM - 1) / kTileM), n_ct = Cout / kTileN;
-  // persistent: one block of 4 waves per CU (the register budget admits one wave per SIMD); 32 blocks per XCD
-  const int blocks = 256;
   const int S = Cin / kStageK;
 #define EQA_CG_LAUNCH(NP)                                                                                                        \
-  hipLaunchKernelGGL(fft_cgemm3m_kernel<NP>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, V, B3, Mo, (int)M,                 \
-                     (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rt, n_ct, (blocks / kXcd) * 4)
+  hipLaunchKernelGGL(fft_cgemm3m_kernel<NP>, dim3(kGridBlocks), dim3(256), 0, (hipStream_t)stream, V, B3, Mo, (int)M,            \
+                     (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rt, n_ct, kWavesPerXcd)
   switch (32 % S == 0 ? 32 / S : 0) {     // (16 pairs per stage -- 32 channels -- would need 64 registers to park them: dynamic form)
     case 8: EQA_CG_LAUNCH(8); break;      // 64 channels (the reference tutorial's 16 x C4): 4 stages, 8 row pairs leave per stage
     case 4: EQA_CG_LAUNCH(4); break;
@@ -490,10 +363,9 @@ int eqa_fft48k5_wgrad3m(const float* V, const float* G, float* D, int64_t M, int
     return EQA_ERR_UNSUPPORTED;
   const int n_it = Cin / 64, n_ot = Cout / 64;
   if ((int64_t)F * n_it * n_ot > 0x7fffffffLL) return EQA_ERR_UNSUPPORTED;
-  const int blocks = 256;
-  hipLaunchKernelGGL(fft_wgrad3m_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, V, G, D, (int)M, (int)eqa_fft48k5_tile_pitch(M),
-                     Cin, Cout, F, n_it, n_ot, (blocks / kXcd) * 4);
-  return hipGetLastError() == hipSuccess ? EQA_OK : EQA_ERR_LAUNCH;
+  hipLaunchKernelGGL(fft_wgrad3m_kernel, dim3(kGridBlocks), dim3(256), 0, (hipStream_t)stream, V, G, D, (int)M,
+                     (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_it, n_ot, kWavesPerXcd);
+  return launch_status();
 }
 
 }  // extern "C"

@@ -22,17 +22,74 @@
 // channel 16 s + 8 b + 4 h + t on both sides.
 #include "eqa_common.hpp"
 
+// The one debug build that is kept (tools/kbench_gemm_clock.py): -DEQA_BLK_CLOCK=1 stamps the first / last shader cycle and the
+// constant 100 MHz counter of block 100's first thread and the cycles of its tile epilogues; =2 adds an s_memtime at every region
+// boundary of a K-stage.  The product build's BlkClock is empty: the block kernel calls it unconditionally.
+#ifdef EQA_BLK_CLOCK
+namespace {
+__device__ long long g_blk_clock[16];
+struct BlkClock {
+  long long c0, w0, e0, t_epi;
+  unsigned long long tk[8], tot[8];
+  __device__ __forceinline__ BlkClock() : c0(clock64()), w0(wall_clock64()), e0(0), t_epi(0), tk{}, tot{} {}
+  __device__ __forceinline__ void tick(int i) {
+    if constexpr (EQA_BLK_CLOCK >= 2) {
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_memtime %0" : "=s"(tk[i]));
+    }
+  }
+  __device__ __forceinline__ void stage_end() {          // behind the stage's barrier
+    if constexpr (EQA_BLK_CLOCK >= 2) {
+      tick(5);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int i = 0; i < 5; ++i) tot[i] += tk[i + 1] - tk[i];
+    }
+  }
+  __device__ __forceinline__ void tile_epilogue_begin() { e0 = clock64(); }
+  __device__ __forceinline__ void tile_epilogue_end() { t_epi += clock64() - e0; }
+  __device__ __forceinline__ void publish() {
+    if (blockIdx.x == 100 && threadIdx.x == 0) {
+      g_blk_clock[0] = clock64() - c0; g_blk_clock[1] = wall_clock64() - w0; g_blk_clock[2] = t_epi;
+      for (int i = 0; i < 7; ++i) g_blk_clock[3 + i] = (long long)tot[i];
+    }
+  }
+};
+}  // namespace
+extern "C" int eqa_debug_blk_clock(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_blk_clock), 80); }
+#else
+namespace {
+struct BlkClock {
+  __device__ __forceinline__ void tick(int) {}
+  __device__ __forceinline__ void stage_end() {}
+  __device__ __forceinline__ void tile_epilogue_begin() {}
+  __device__ __forceinline__ void tile_epilogue_end() {}
+  __device__ __forceinline__ void publish() {}
+};
+}  // namespace
+#endif
+
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "cgemm3m_common.inc"   // the wave-tile walk, the buffer descriptors, the parked tile: shared with cgemm3m.hip
 
-constexpr int kTileM = 64, kTileN = 64;
-constexpr int kStageK = 16;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
 constexpr unsigned kHi = 0xffff0000u;
+
+// The three-piece split of one value: bit patterns whose top 16 bits are p1, p2, p3 (x = p1 + p2 + p3)
+__device__ __forceinline__ void split3(const float a, unsigned (&x)[3]) {
+  const float p1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, a) & kHi);
+  const float r1 = a - p1;                                       // exact: the low 16 bits of the significand
+  const float p2 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & kHi);
+  const float r2 = r1 - p2;                                      // exact: at most 8 significant bits -> a bf16 as it stands
+  x[0] = __builtin_bit_cast(unsigned, a);
+  x[1] = __builtin_bit_cast(unsigned, r1);
+  x[2] = __builtin_bit_cast(unsigned, r2);
+}
+// the high halves of two such patterns -> one dword of two bf16 (v_perm_b32)
+__device__ __forceinline__ unsigned pack_hi(const unsigned lo, const unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
 
 // 8 fp32 values (two 16-byte loads) -> three packed operands of the bf16 instruction
 struct Pieces {
@@ -40,29 +97,25 @@ struct Pieces {
 };
 __device__ __forceinline__ Pieces split8(const f32x4 lo, const f32x4 hi) {
   Pieces o;
-#ifdef EQA_CGEMM_NOSPLIT      // experiment: no split arithmetic (wrong values): what the kernel costs without its vector work
-  o.p[0] = __builtin_bit_cast(u32x4, lo); o.p[1] = __builtin_bit_cast(u32x4, hi); o.p[2] = __builtin_bit_cast(u32x4, lo);
-  return o;
-#endif
-  unsigned x0[8], x1[8], x2[8];
+  unsigned x[8][3];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float a = e < 4 ? lo[e & 3] : hi[e & 3];
-    const float p1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, a) & kHi);
-    const float r1 = a - p1;                                       // exact: the low 16 bits of the significand
-    const float p2 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & kHi);
-    const float r2 = r1 - p2;                                      // exact: at most 8 significant bits -> a bf16 as it stands
-    x0[e] = __builtin_bit_cast(unsigned, a);
-    x1[e] = __builtin_bit_cast(unsigned, r1);
-    x2[e] = __builtin_bit_cast(unsigned, r2);
-  }
+  for (int e = 0; e < 8; ++e) split3(e < 4 ? lo[e & 3] : hi[e & 3], x[e]);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {                                    // the high halves of two floats -> one dword (v_perm_b32)
-    o.p[0][j] = __builtin_amdgcn_perm(x0[2 * j + 1], x0[2 * j], 0x07060302u);
-    o.p[1][j] = __builtin_amdgcn_perm(x1[2 * j + 1], x1[2 * j], 0x07060302u);
-    o.p[2][j] = __builtin_amdgcn_perm(x2[2 * j + 1], x2[2 * j], 0x07060302u);
-  }
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) o.p[q][j] = pack_hi(x[2 * j][q], x[2 * j + 1][q]);
   return o;
+}
+// 4 values -> their three pieces, 8 bytes each
+__device__ __forceinline__ void split4(const f32x4 v, u32x2 (&o)[3]) {
+  unsigned x[4][3];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) split3(v[t], x[t]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    o[q][0] = pack_hi(x[0][q], x[1][q]);
+    o[q][1] = pack_hi(x[2][q], x[3][q]);
+  }
 }
 
 // Registers: 192 accumulators (AGPRs) leave 256 + 64 for everything else, and the register allocator shuttles operands between
@@ -80,29 +133,21 @@ struct APieces {
   Pieces a[2][3];                // [m][part]
 };
 
-struct StageAddr {
-  __amdgpu_buffer_rsrc_t a, b;
-  unsigned sa, sb;
-};
-
-__device__ __forceinline__ u32x4 buf_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-
 constexpr unsigned kBFrag = 64 * 16;    // bytes of one (part, piece) fragment of a 32-column tile
+constexpr unsigned kBTileBytes = 9 * kBFrag;   // Bp per (K-stage, 32-column tile): [part r/i/s][piece]
 
 __device__ __forceinline__ void load_a(ARaw& o, const StageAddr& at, unsigned aoff) {
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
-    o.ar[b] = __builtin_bit_cast(f32x4, buf_ld(at.a, aoff + 32 * b, at.sa));
-    o.ai[b] = __builtin_bit_cast(f32x4, buf_ld(at.a, aoff + 32 * b + 64, at.sa));
+    o.ar[b] = buf_ld<f32x4>(at.a, aoff + 32 * b, at.sa);
+    o.ai[b] = buf_ld<f32x4>(at.a, aoff + 32 * b + 64, at.sa);
   }
 }
 __device__ __forceinline__ void load_b(BHalf& o, const StageAddr& at, unsigned boff, int n) {
 #pragma unroll
   for (int p = 0; p < 3; ++p)
 #pragma unroll
-    for (int q = 0; q < 3; ++q) o.b[p][q] = buf_ld(at.b, boff + ((n * 3 + p) * 3 + q) * kBFrag, at.sb);
+    for (int q = 0; q < 3; ++q) o.b[p][q] = buf_ld<u32x4>(at.b, boff + ((n * 3 + p) * 3 + q) * kBFrag, at.sb);
 }
 
 __device__ __forceinline__ void split_a(APieces& P, const ARaw& r, int m) {
@@ -129,22 +174,6 @@ __device__ __forceinline__ void mma_quarter(const APieces& P, const BHalf& B, f3
     }
 }
 
-constexpr int kLdsRowFloats = 2 * kTileN;
-constexpr int kLdsWaveFloats = kTileM * kLdsRowFloats;
-
-struct ParkedDst {
-  __amdgpu_buffer_rsrc_t rsrc;
-  int voff, pair_bytes;
-  unsigned soff;
-};
-
-__device__ __forceinline__ void store_pair(const ParkedDst& d, int p, f32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), d.rsrc, d.voff + p * d.pair_bytes, d.soff, 0);
-}
-__device__ __forceinline__ void flush_rows(const float* lds_lane, const ParkedDst& d, int p0, int p1) {
-  for (int p = p0; p < p1; ++p) store_pair(d, p, *reinterpret_cast<const f32x4*>(lds_lane + p * (2 * kLdsRowFloats)));
-}
-
 // One K-stage = four quarters (column half n, row half m), 3 x TERMS matrix instructions each, every quarter one scheduling region
 // in which the instruction order is pinned: the wave issues in order, so whatever is to run in the shadow of the matrix pipe has
 // to sit BETWEEN two matrix instructions.
@@ -158,7 +187,6 @@ __device__ __forceinline__ void flush_rows(const float* lds_lane, const ParkedDs
 // B0 = this stage's column half 0.
 template <int NMMA, int NVALU, int NLOAD, int NSTORE, int NDS>
 __device__ __forceinline__ void pin_quarter() {
-#ifndef EQA_CGEMM_BF16_NOPIN
   if (NDS) __builtin_amdgcn_sched_group_barrier(0x100, NDS, 0);
   constexpr int kMem = NLOAD + NSTORE;
   constexpr int kValuPer = (NVALU + NMMA - 1) / NMMA;
@@ -169,34 +197,23 @@ __device__ __forceinline__ void pin_quarter() {
     else if (k < kMem) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);    // ... then the stores
     if (NVALU) __builtin_amdgcn_sched_group_barrier(0x002, kValuPer, 0);     // its share of the vector arithmetic
   }
-#endif
 }
 
 template <int NPAIR, int TERMS>
 __device__ __forceinline__ void run_stage(APieces& P, ARaw& raw0, ARaw& raw1, BHalf& B0, BHalf& B1, f32x16 (&acc)[3][2][2],
                                           const StageAddr& cur, const StageAddr& nxt, unsigned naoff0, unsigned naoff1, unsigned boff,
-                                          const float* lds_lane, const ParkedDst& dst, int p0, const StageAddr& far, unsigned far_off,
-                                          unsigned& touch) {
+                                          const float* lds_lane, const ParkedDst& dst, int p0) {
   constexpr int kQ = 3 * TERMS;          // matrix instructions per quarter
   constexpr int kSplit = 150;            // vector instructions of one row half's split (an upper bound for the pinning)
   f32x4 park[NPAIR > 0 ? NPAIR : 1];
   __builtin_amdgcn_sched_barrier(0);
-#ifdef EQA_CGEMM_TOUCH     // experiment, measured SLOWER (3.46 vs 3.32 ms): not the missing look-ahead
-  // A stage is 1.8 us of matrix instructions and A is requested three quarters of a stage ahead: less than an HBM round trip
-  // under load.  One dword per lane (= per row of the tile: a row's stage is one 128-byte line) of the stage kPrefetch ahead pulls
-  // those lines into L2 early; the value is never used (the previous stage's is retired here, a stage after its request).
-  asm volatile("" ::"v"(touch));
-  touch = __builtin_amdgcn_raw_buffer_load_b32(far.a, far_off, far.sa, 0);
-#endif
+  // (Tried: one dword per lane of A three stages ahead, to pull the lines into L2 early -- SLOWER, 3.455 vs 3.32 ms:
+  // profiles/r04/kbench_gemm_pieces.txt.  A's three quarters of a stage of lead are not what is missing.)
   load_b(B1, cur, boff, 1);
   load_a(raw0, nxt, naoff0);
   split_a(P, raw1, 1);
   mma_quarter<TERMS>(P, B0, acc, 0, 0);
-#ifdef EQA_CGEMM_TOUCH
-  pin_quarter<kQ, kSplit, 14, 0, 0>();
-#else
   pin_quarter<kQ, kSplit, 13, 0, 0>();
-#endif
   __builtin_amdgcn_sched_barrier(0);
   load_a(raw1, nxt, naoff1);
   mma_quarter<TERMS>(P, B0, acc, 1, 0);
@@ -233,63 +250,14 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_kernel(const float* _
   __shared__ __attribute__((aligned(16))) float lds_all[4 * kLdsWaveFloats];
   float* lds_w = lds_all + wave * kLdsWaveFloats;
   const float* lds_lane = lds_w + h * kLdsRowFloats + i * 4;
-  const size_t rowf = (size_t)2 * Cin, mo_row = (size_t)2 * Cout;
-  const unsigned b_stage_bytes = (unsigned)(Cout / 32) * 9 * kBFrag;        // bytes per (f, stage) of Bp
-  const unsigned a_stage = 32u * 4u;
+  const WaveTileWalk<uint16_t, kBTileBytes> walk(V, Bp, Mo, M, pitch, Cin, Cout, xcd, wpf, n_ct, S, i, h);
   const unsigned boff = lane * 16;
-
-  auto locate = [&](int u, StageAddr& at, unsigned& aoff0, unsigned& aoff1, int& f, int& row0, int& ct, unsigned& toff) {
-#ifdef EQA_CGEMM_SAMETILE     // experiment: every wave-tile reads tile 0 -- operands always cached
-    u = 0;
-#endif
-    const int fi = u / wpf, r = u - fi * wpf;
-    f = xcd + kXcd * fi;
-    const int rt = r / n_ct;
-    ct = r - rt * n_ct;
-    row0 = rt * kTileM;
-#ifdef EQA_CGEMM_SAME_A      // experiment: A always from (frequency 0, row tile 0)
-    at.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V), 0, (unsigned)((size_t)pitch * rowf * 4), 0x00020000);
-    at.sa = 0;
-    aoff0 = (unsigned)((size_t)i * rowf + 4 * h) * 4u;
-#else
-    at.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V) + (size_t)f * pitch * rowf, 0, (unsigned)((size_t)pitch * rowf * 4), 0x00020000);
-    at.sa = 0;
-    aoff0 = (unsigned)((size_t)(row0 + i) * rowf + 4 * h) * 4u;
-#endif
-    aoff1 = aoff0 + 32 * (unsigned)rowf * 4u;
-    toff = (unsigned)((size_t)(row0 + lane) * rowf) * 4u;                  // row `lane` of the tile: the prefetch touch
-#ifdef EQA_CGEMM_SAME_B      // experiment: B always from (frequency 0, column tile 0)
-    at.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Bp), 0, (unsigned)S * b_stage_bytes, 0x00020000);
-    at.sb = 0;
-#else
-    at.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Bp) + (size_t)f * S * (b_stage_bytes / 2), 0, (unsigned)S * b_stage_bytes, 0x00020000);
-    at.sb = (unsigned)(2 * ct) * (9 * kBFrag);
-#endif
-  };
-  auto at_stage = [&](const StageAddr& t, int s) { return StageAddr{t.a, t.b, t.sa + s * a_stage, t.sb + s * b_stage_bytes}; };
-  auto parked = [&](int f, int row0, int ct) {
-    const int rows = min(kTileM, M - row0);
-    ParkedDst d;
-#ifdef EQA_CGEMM_NOSTORE     // experiment: an empty buffer drops the stores
-    d.rsrc = __builtin_amdgcn_make_buffer_rsrc(Mo, 0, 0, 0x00020000);
-#else
-    d.rsrc = __builtin_amdgcn_make_buffer_rsrc(Mo + ((size_t)f * pitch + row0) * mo_row, 0, (unsigned)(rows * mo_row * 4), 0x00020000);
-#endif
-    d.voff = (h * (int)mo_row + ct * kLdsRowFloats + i * 4) * 4;
-    d.pair_bytes = 2 * (int)mo_row * 4;
-    d.soff = 0;
-    return d;
-  };
 
   StageAddr at;
   unsigned aoff0, aoff1;
   int f, row0, ct;
-  unsigned toff;
-  locate(q, at, aoff0, aoff1, f, row0, ct, toff);
-  ParkedDst dst = parked(f, row0, ct);
-  unsigned touch = 0;
-  constexpr int kPrefetch = 3;             // stages between the touch of a row's line and the request of its operands
-  dst.rsrc = __builtin_amdgcn_make_buffer_rsrc(Mo, 0, 0, 0x00020000);       // nothing parked yet: an empty buffer drops the stores
+  walk.locate(q, at, aoff0, aoff1, f, row0, ct);
+  ParkedDst dst = walk.nothing_parked(f, row0, ct);
   ARaw raw0, raw1;
   APieces P;
   BHalf B0, B1;
@@ -307,39 +275,22 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_kernel(const float* _
         for (int n = 0; n < 2; ++n)
 #pragma unroll
           for (int e = 0; e < 16; ++e) acc[p][m][n][e] = 0.f;
-    const int un = u + waves_per_xcd < total ? u + waves_per_xcd : u;
+    // the tile after this one (or this one again when it is the last: a harmless reload instead of a conditional load)
     StageAddr nat;
-    unsigned naoff0, naoff1, ntoff;
+    unsigned naoff0, naoff1;
     int nf, nrow0, nct;
-    locate(un, nat, naoff0, naoff1, nf, nrow0, nct, ntoff);
+    walk.locate(u + waves_per_xcd < total ? u + waves_per_xcd : u, nat, naoff0, naoff1, nf, nrow0, nct);
     for (int s = 0; s < S; ++s) {
       const bool more = s + 1 < S;
       if (NPAIR == 0) flush_rows(lds_lane, dst, (32 * s) / S, (32 * (s + 1)) / S);
-      const bool far_here = s + kPrefetch < S;   // (S < kPrefetch: the touches run into the next tile's later stages -- harmless)
-      run_stage<NPAIR, TERMS>(P, raw0, raw1, B0, B1, acc, at_stage(at, s), more ? at_stage(at, s + 1) : nat, more ? aoff0 : naoff0,
-                              more ? aoff1 : naoff1, boff, lds_lane, dst, s * NPAIR,
-                              far_here ? at_stage(at, s + kPrefetch) : at_stage(nat, s + kPrefetch - S), far_here ? toff : ntoff, touch);
+      run_stage<NPAIR, TERMS>(P, raw0, raw1, B0, B1, acc, walk.at_stage(at, s), more ? walk.at_stage(at, s + 1) : nat,
+                              more ? aoff0 : naoff0, more ? aoff1 : naoff1, boff, lds_lane, dst, s * NPAIR);
     }
-    // epilogue: Cr = T1 - T2, Ci = T3 - T1 - T2 into the wave's LDS tile (accumulator layout = that of the fp32 instruction)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int r = 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-          const float t1 = acc[0][m][n][e], t2 = acc[1][m][n][e], t3 = acc[2][m][n][e];
-          f32x2v c;
-          c[0] = t1 - t2;
-          c[1] = t3 - t1 - t2;
-          *reinterpret_cast<f32x2v*>(lds_w + r * kLdsRowFloats + (32 * n + i) * 2) = c;
-        }
-      }
-    dst = parked(f, row0, ct);
-    at = nat; aoff0 = naoff0; aoff1 = naoff1; f = nf; row0 = nrow0; ct = nct; toff = ntoff;
+    park_tile(acc, lds_w, i, h);
+    dst = walk.parked(f, row0, ct);
+    at = nat; aoff0 = naoff0; aoff1 = naoff1; f = nf; row0 = nrow0; ct = nct;
   }
-  asm volatile("" ::"v"(touch));
-  flush_rows(lds_lane, dst, 0, 32);
+  flush_rows(lds_lane, dst, 0, 32);       // the wave's last tile
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -365,7 +316,6 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_kernel(const float* _
 constexpr int kBlkM = 128, kBlkN = 128;
 constexpr int kFragBytes = 64 * 16;
 constexpr int kABufs = 3;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // TERMS = 3: the fp16 form.  An fp32 operand x, scaled by a power of two into the top of the fp16 range, is split into TWO fp16
@@ -394,33 +344,9 @@ struct TileAt {                   // uniform: where a block tile's operands are
   unsigned sb;
 };
 
-__device__ __forceinline__ void split4(const f32x4 v, u32x2 (&o)[3]) {
-  unsigned x[3][4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const float a = v[t];
-    const float p1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, a) & kHi);
-    const float r1 = a - p1;
-    const float p2 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & kHi);
-    const float r2 = r1 - p2;
-    x[0][t] = __builtin_bit_cast(unsigned, a);
-    x[1][t] = __builtin_bit_cast(unsigned, r1);
-    x[2][t] = __builtin_bit_cast(unsigned, r2);
-  }
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    o[q][0] = __builtin_amdgcn_perm(x[q][1], x[q][0], 0x07060302u);
-    o[q][1] = __builtin_amdgcn_perm(x[q][3], x[q][2], 0x07060302u);
-  }
-}
 // two fp16 pieces of four (already scaled) values: v_cvt_pk_f16_f32 (round to nearest even), the remainder, again
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split4h(const f32x4 v, u32x2 (&o)[2]) {
-#ifdef EQA_BLK_NOSPLIT       // ablation: no split arithmetic (wrong values)
-  o[0][0] = __builtin_bit_cast(unsigned, v[0]) & 0x3fff3fffu; o[0][1] = __builtin_bit_cast(unsigned, v[1]) & 0x3fff3fffu;
-  o[1][0] = __builtin_bit_cast(unsigned, v[2]) & 0x3fff3fffu; o[1][1] = __builtin_bit_cast(unsigned, v[3]) & 0x3fff3fffu;
-  return;
-#endif
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const float a = v[2 * j], b = v[2 * j + 1];
@@ -443,19 +369,16 @@ __device__ __forceinline__ void split_part(const RawA& r, unsigned char* wr, con
 }
 template <int ROW>
 __device__ __forceinline__ void load_raw(RawA& o, const TileAt& t, unsigned voff, unsigned row64, unsigned soff) {
-  o.re[ROW] = __builtin_bit_cast(f32x4, buf_ld(t.a, voff + ROW * row64, soff));
-  o.im[ROW] = __builtin_bit_cast(f32x4, buf_ld(t.a, voff + ROW * row64 + 64, soff));
+  o.re[ROW] = buf_ld<f32x4>(t.a, voff + ROW * row64, soff);
+  o.im[ROW] = buf_ld<f32x4>(t.a, voff + ROW * row64 + 64, soff);
 }
 template <int NP>
 __device__ __forceinline__ void load_bset(BSet<NP>& o, const TileAt& t, unsigned voff, unsigned soff) {
 #pragma unroll
-  for (int k = 0; k < 3 * NP; ++k) o.b[k / NP][k % NP] = buf_ld(t.b, voff + k * kBFrag, t.sb + soff);
+  for (int k = 0; k < 3 * NP; ++k) o.b[k / NP][k % NP] = buf_ld<u32x4>(t.b, voff + k * kBFrag, t.sb + soff);
 }
 template <int NP, int M, int PA>
 __device__ __forceinline__ void read_frags(AFrags& o, const unsigned char* rd) {
-#ifdef EQA_BLK_NOLDSREAD     // ablation: the fragments of (row quarter 0, piece 0) stand for every one (wrong values)
-  if (M != 0 || PA != 0) return;
-#endif
 #pragma unroll
   for (int p = 0; p < 3; ++p) o.a[p] = *reinterpret_cast<const u32x4*>(rd + ((M * 3 + p) * NP + PA) * kFragBytes);
 }
@@ -478,7 +401,6 @@ __device__ __forceinline__ void mma_rows(const AFrags& A, const BSet<pieces_of(T
 // the order of a region's instructions: behind each matrix instruction its share of the LDS reads, loads, vector arithmetic, writes
 template <int NMMA, int NDSR, int NLOAD, int NVALU, int NDSW>
 __device__ __forceinline__ void pin_region() {
-#ifndef EQA_CGEMM_BF16_NOPIN
   constexpr int kValuPer = (NVALU + NMMA - 1) / NMMA;
 #pragma unroll
   for (int k = 0; k < NMMA; ++k) {
@@ -488,14 +410,7 @@ __device__ __forceinline__ void pin_region() {
     if (NVALU) __builtin_amdgcn_sched_group_barrier(0x002, kValuPer, 0);
     if (k >= NMMA - NDSW) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
   }
-#endif
 }
-
-#if defined(EQA_BLK_CLOCK) && EQA_BLK_CLOCK >= 2
-#define EQA_TICK(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0" : "=s"(tk[i])); } while (0)
-#else
-#define EQA_TICK(i)
-#endif
 
 // One K-stage.  On entry: Bc = this stage's B, F0 = the fragments (row quarter 0, piece 0), raw = the raw values of stage g + 2
 // (arrived); rd / rd_next = this lane's read address in this stage's / the next stage's LDS buffer, wr = its write address in
@@ -505,19 +420,12 @@ __device__ __forceinline__ void run_stage_block(const BSet<pieces_of(TERMS)>& Bc
                                                 AFrags& F1, AFrags& F2, AFrags& F3,
                                                 f32x16 (&acc)[3][4], const unsigned char* rd, const unsigned char* rd_next,
                                                 unsigned char* wr, const TileAt& tb, unsigned sb_off, unsigned b_voff, const TileAt& ta,
-                                                unsigned sa_off, unsigned a_voff, unsigned row64, const float scale
-#ifdef EQA_BLK_CLOCK
-                                                , unsigned long long (&tot)[8]
-#endif
-                                                ) {
-#ifdef EQA_BLK_CLOCK
-  unsigned long long tk[8];
-#endif
+                                                unsigned sa_off, unsigned a_voff, unsigned row64, const float scale, BlkClock& clk) {
   constexpr int NP = pieces_of(TERMS);
   constexpr int kN = TERMS == 9 ? 27 : TERMS == 6 ? 18 : 9;   // matrix instructions of a region
   constexpr int kSplit = NP == 3 ? 32 : 20;                   // vector instructions of one split_part (an upper bound for the pinning)
   constexpr int kRd = 3 * NP;                                 // fragments a region reads: pieces 1.. of its row quarter, piece 0 of the next
-  EQA_TICK(0);
+  clk.tick(0);
   // region m = 0: B of the next stage; row r: re
   __builtin_amdgcn_sched_barrier(0);
   read_frags<NP, 0, 1>(F1, rd);
@@ -528,7 +436,7 @@ __device__ __forceinline__ void run_stage_block(const BSet<pieces_of(TERMS)>& Bc
   mma_rows<TERMS, 0, 0, FIRST>(F0, Bc, acc); mma_rows<TERMS, 0, 1, FIRST>(F1, Bc, acc);
   if constexpr (NP == 3) mma_rows<TERMS, 0, 2, FIRST>(F2, Bc, acc);
   pin_region<kN, kRd, kRd, kSplit, NP>();
-  EQA_TICK(1);
+  clk.tick(1);
   // region m = 1: row r: im, re + im
   __builtin_amdgcn_sched_barrier(0);
   read_frags<NP, 1, 1>(F1, rd);
@@ -538,7 +446,7 @@ __device__ __forceinline__ void run_stage_block(const BSet<pieces_of(TERMS)>& Bc
   mma_rows<TERMS, 1, 0, FIRST>(F3, Bc, acc); mma_rows<TERMS, 1, 1, FIRST>(F1, Bc, acc);
   if constexpr (NP == 3) mma_rows<TERMS, 1, 2, FIRST>(F2, Bc, acc);
   pin_region<kN, kRd, 0, 2 * kSplit + 4, 2 * NP>();
-  EQA_TICK(2);
+  clk.tick(2);
   // region m = 2: row r + 64: re, im
   __builtin_amdgcn_sched_barrier(0);
   read_frags<NP, 2, 1>(F1, rd);
@@ -548,7 +456,7 @@ __device__ __forceinline__ void run_stage_block(const BSet<pieces_of(TERMS)>& Bc
   mma_rows<TERMS, 2, 0, FIRST>(F0, Bc, acc); mma_rows<TERMS, 2, 1, FIRST>(F1, Bc, acc);
   if constexpr (NP == 3) mma_rows<TERMS, 2, 2, FIRST>(F2, Bc, acc);
   pin_region<kN, kRd, 0, 2 * kSplit, 2 * NP>();
-  EQA_TICK(3);
+  clk.tick(3);
   // region m = 3: row r + 64: re + im; the raw values of stage g + 4
   __builtin_amdgcn_sched_barrier(0);
   read_frags<NP, 3, 1>(F1, rd);
@@ -561,25 +469,13 @@ __device__ __forceinline__ void run_stage_block(const BSet<pieces_of(TERMS)>& Bc
   pin_region<kN, kRd, 2, kSplit + 4, NP>();
   __builtin_amdgcn_sched_barrier(0);
   load_raw<1>(raw, ta, a_voff, row64, sa_off);
-  EQA_TICK(4);
+  clk.tick(4);
   __builtin_amdgcn_sched_barrier(0);
   // the stage's pieces are written (mine: lgkmcnt), every wave is done with the buffer that stage g + 3 will be built in
-#ifdef EQA_BLK_NOBARRIER
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-#if defined(EQA_BLK_CLOCK) && EQA_BLK_CLOCK >= 2
-  EQA_TICK(5);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < 5; ++i) tot[i] += tk[i + 1] - tk[i];
-#endif
+  clk.stage_end();
 }
 
-#ifdef EQA_BLK_CLOCK
-__device__ long long g_blk_clock[16];
-#endif
 template <int TERMS>
 __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_block_kernel(const float* __restrict__ V, const uint16_t* __restrict__ Bp,
                                                                         float* __restrict__ Mo, int M, int pitch, int Cin, int Cout, int F,
@@ -596,14 +492,7 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_block_kernel(const fl
   const int nf_x = (F - xcd + kXcd - 1) / kXcd;
   const int total = nf_x * tpf;
   if (q >= total) return;
-#ifdef EQA_BLK_CLOCK
-  const long long c0 = clock64(), w0 = wall_clock64();
-  unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long t_epi = 0;
-#define EQA_TOT , tot
-#else
-#define EQA_TOT
-#endif
+  BlkClock clk;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // kABufs * kAStageBytes
   const size_t rowf = (size_t)2 * Cin, mo_row = (size_t)2 * Cout;
   const unsigned b_stage_bytes = (unsigned)(Cout / 32) * 3 * NP * kBFrag;
@@ -627,17 +516,8 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_block_kernel(const fl
     // past the block's last tile: empty descriptors (the look-ahead reads zeros, no traffic); rows past the pitch likewise
     at.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V) + (size_t)f * pitch * rowf, 0, live ? (unsigned)((size_t)pitch * rowf * 4) : 0u, 0x00020000);
     aoff = (unsigned)((size_t)(row0 + sp_row) * rowf * 4) + sp_k;
-#ifdef EQA_BLK_SAME_B
-    at.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Bp), 0, live ? (unsigned)S * b_stage_bytes : 0u, 0x00020000);
-    at.sb = 0;
-#else
     at.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Bp) + (size_t)f * S * (b_stage_bytes / 2), 0, live ? (unsigned)S * b_stage_bytes : 0u, 0x00020000);
     at.sb = (unsigned)ct * (3 * NP * kBFrag);
-#endif
-#ifdef EQA_BLK_SAME_A
-    at.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(V), 0, live ? (unsigned)((size_t)pitch * rowf * 4) : 0u, 0x00020000);
-    aoff = (unsigned)((size_t)(sp_row) * rowf * 4) + sp_k;
-#endif
   };
 
   // three positions in the block's sequence of K-stages: A's loads (4 stages ahead), B's loads (1 ahead), the matrix instructions
@@ -697,7 +577,7 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_block_kernel(const fl
   {                                                                                                                                  \
     const unsigned r1 = step(rbuf), r2 = step(r1);                                                                                   \
     run_stage_block<TERMS, FIRST>(BC, BN, RAW, F0, F1, F2, F3, acc, lds + rbuf + lane * 16, lds + r1 + lane * 16, lds + r2 + sp_lds, \
-                                  tb, sb * b_stage_bytes, b_voff, ta, sa * a_stage, a_voff, row64, a_scale EQA_TOT);                          \
+                                  tb, sb * b_stage_bytes, b_voff, ta, sa * a_stage, a_voff, row64, a_scale, clk);                            \
     next_a(); next_b();                                                                                                              \
     rbuf = r1;                                                                                                                       \
   }
@@ -709,17 +589,11 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_block_kernel(const fl
     }
 #undef EQA_STAGE
     // Cr = T1 - T2, Ci = T3 - T1 - T2, straight from the accumulators: lane (i, h), slot e = row (e & 3) + 8 (e >> 2) + 4 h, column i
-#ifdef EQA_BLK_CLOCK
-    const long long e0 = clock64();
-#endif
+    clk.tile_epilogue_begin();
     {
       const int rows = __builtin_amdgcn_readfirstlane(min(kBlkM, M - row0));
-#ifdef EQA_BLK_NOSTORE
-      const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(Mo, 0, (unsigned)(rows * 0), 0x00020000);
-#else
       const __amdgpu_buffer_rsrc_t dr =
           __builtin_amdgcn_make_buffer_rsrc(Mo + ((size_t)f * pitch + row0) * mo_row, 0, (unsigned)(rows * mo_row * 4), 0x00020000);
-#endif
       const int i = lane & 31, h = lane >> 5;
       const unsigned voff = (unsigned)((4 * h * mo_row + (size_t)(32 * ct + i) * 2) * 4);
 #pragma unroll
@@ -739,16 +613,9 @@ __global__ __launch_bounds__(256, 1) void fft_cgemm3m_bf16_block_kernel(const fl
     unsigned unused_o;
     locate(u + blocks_per_xcd, unused_t, unused_o, nf, nrow0, nct);
     f = nf; row0 = nrow0; ct = nct;
-#ifdef EQA_BLK_CLOCK
-    t_epi += clock64() - e0;
-#endif
+    clk.tile_epilogue_end();
   }
-#ifdef EQA_BLK_CLOCK
-  if (blockIdx.x == 100 && threadIdx.x == 0) {
-    g_blk_clock[0] = clock64() - c0; g_blk_clock[1] = wall_clock64() - w0; g_blk_clock[2] = t_epi;
-    for (int i = 0; i < 7; ++i) g_blk_clock[3 + i] = (long long)tot[i];
-  }
-#endif
+  clk.publish();
 }
 
 // B3 (F, S, Cout/32, 3, 2, 64, 4) fp32 -> Bp (F, S, Cout/32, 3, 3, 64, 8) bf16: one thread per (f, s, column tile, part, lane)
@@ -786,6 +653,19 @@ __global__ __launch_bounds__(256) void spectra3m_split_f16_kernel(const float* _
   }
 }
 
+// the block form's launch: 128 x 128 tiles, one block per CU, three K-stages of A's pieces in dynamic LDS
+template <int TERMS>
+int launch_block(const float* V, const void* B, float* Mo, int64_t M, int Cin, int Cout, const float* vbound, int nbound, float b_scale,
+                 void* stream) {
+  const int n_rb = (int)((M + kBlkM - 1) / kBlkM), n_cg = Cout / kBlkN;
+  constexpr int kLds = kABufs * a_stage_bytes(TERMS);
+  if (!allow_dynamic_lds((const void*)fft_cgemm3m_bf16_block_kernel<TERMS>, kLds)) return EQA_ERR_LAUNCH;
+  hipLaunchKernelGGL((fft_cgemm3m_bf16_block_kernel<TERMS>), dim3(kGridBlocks), dim3(256), kLds, (hipStream_t)stream, V,
+                     static_cast<const uint16_t*>(B), Mo, (int)M, (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, eqa_fft48k5_frequencies(), n_rb,
+                     n_cg, kBlocksPerXcd, vbound, nbound, b_scale);
+  return launch_status();
+}
+
 }  // namespace
 
 namespace eqa {
@@ -799,10 +679,6 @@ int64_t eqa_fft48k5_spectra3m_bf16_bytes(int Cin, int Cout) {
   return (int64_t)eqa_fft48k5_frequencies() * Cin * Cout * 3 * 3 * 2;
 }
 
-#ifdef EQA_BLK_CLOCK
-int eqa_debug_blk_clock(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_blk_clock), 80); }
-#endif
-
 int eqa_fft48k5_spectra3m_split(const float* B3, void* Bp, int Cin, int Cout, void* stream) {
   if (!B3 || !Bp) return EQA_ERR_INVALID_ARG;
   if (!eqa_fft48k5_cgemm3m_supported(Cin, Cout) || (((uintptr_t)B3 | (uintptr_t)Bp) & 15)) return EQA_ERR_UNSUPPORTED;
@@ -814,34 +690,20 @@ int eqa_fft48k5_spectra3m_split(const float* B3, void* Bp, int Cin, int Cout, vo
 }
 
 int eqa_fft48k5_cgemm3m_bf16x3(const float* V, const void* Bp, float* Mo, int64_t M, int Cin, int Cout, int terms, void* stream) {
-  if (!V || !Bp || !Mo || M < 0 || Cin <= 0 || Cout <= 0 || (terms != 9 && terms != 6)) return EQA_ERR_INVALID_ARG;
-  if (M == 0) return EQA_OK;
-  const int F = eqa_fft48k5_frequencies();
-  const int64_t fm_bytes = ((M | 1) + 64) * 2 * (int64_t)std::max(Cin, Cout) * 4;
-  if (!eqa_fft48k5_cgemm3m_supported(Cin, Cout) || M > 0x3fffff || fm_bytes > 0x7fffffffLL || (int64_t)Cin * Cout * 9 * 2 > 0x7fffffffLL ||
-      (((uintptr_t)V | (uintptr_t)Bp | (uintptr_t)Mo) & 15))
-    return EQA_ERR_UNSUPPORTED;
-  const int n_rt = (int)((M + kTileM - 1) / kTileM), n_ct = Cout / kTileN;
-  const int blocks = 256;
-  const int S = Cin / kStageK;
+  if (terms != 9 && terms != 6) return EQA_ERR_INVALID_ARG;
+  const int st = check_contraction_args(V, Bp, Mo, M, Cin, Cout);
+  if (st != EQA_OK) return st == kNothingToDo ? EQA_OK : st;
+  if ((int64_t)Cin * Cout * 9 * 2 > 0x7fffffffLL) return EQA_ERR_UNSUPPORTED;      // one frequency of Bp: a descriptor range
   if (Cout % kBlkN == 0 && eqa::g_cgemm_bf16_form != 1) {      // the block form: A split once per block, shared through LDS
-    const int n_rb = (int)((M + kBlkM - 1) / kBlkM), n_cg = Cout / kBlkN;
-    constexpr int kLds = kABufs * a_stage_bytes(9);
-    const void* kern = terms == 9 ? (const void*)fft_cgemm3m_bf16_block_kernel<9> : (const void*)fft_cgemm3m_bf16_block_kernel<6>;
-    if (!allow_dynamic_lds(kern, kLds)) return EQA_ERR_LAUNCH;
-    if (terms == 9)
-      hipLaunchKernelGGL((fft_cgemm3m_bf16_block_kernel<9>), dim3(blocks), dim3(256), kLds, (hipStream_t)stream, V,
-                         static_cast<const uint16_t*>(Bp), Mo, (int)M, (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rb, n_cg, blocks / kXcd,
-                         (const float*)nullptr, 0, 1.0f);
-    else
-      hipLaunchKernelGGL((fft_cgemm3m_bf16_block_kernel<6>), dim3(blocks), dim3(256), kLds, (hipStream_t)stream, V,
-                         static_cast<const uint16_t*>(Bp), Mo, (int)M, (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rb, n_cg, blocks / kXcd,
-                         (const float*)nullptr, 0, 1.0f);
-    return launch_status();
+    return terms == 9 ? launch_block<9>(V, Bp, Mo, M, Cin, Cout, nullptr, 0, 1.0f, stream)
+                      : launch_block<6>(V, Bp, Mo, M, Cin, Cout, nullptr, 0, 1.0f, stream);
   }
-#define EQA_CG_LAUNCH(NP, T)                                                                                                       \
-  hipLaunchKernelGGL((fft_cgemm3m_bf16_kernel<NP, T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, V, static_cast<const uint16_t*>(Bp), \
-                     Mo, (int)M, (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rt, n_ct, (blocks / kXcd) * 4)
+  const int F = eqa_fft48k5_frequencies();
+  const int n_rt = (int)((M + kTileM - 1) / kTileM), n_ct = Cout / kTileN;
+  const int S = Cin / kStageK;
+#define EQA_CG_LAUNCH(NP, T)                                                                                                            \
+  hipLaunchKernelGGL((fft_cgemm3m_bf16_kernel<NP, T>), dim3(kGridBlocks), dim3(256), 0, (hipStream_t)stream, V,                         \
+                     static_cast<const uint16_t*>(Bp), Mo, (int)M, (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rt, n_ct, kWavesPerXcd)
 #define EQA_CG_TERMS(NP) do { if (terms == 9) EQA_CG_LAUNCH(NP, 9); else EQA_CG_LAUNCH(NP, 6); } while (0)
   switch (32 % S == 0 ? 32 / S : 0) {
     case 4: EQA_CG_TERMS(4); break;
@@ -874,21 +736,12 @@ int eqa_fft48k5_spectra3m_split_f16(const float* B3, void* Bh, int Cin, int Cout
 
 int eqa_fft48k5_cgemm3m_f16x2(const float* V, const void* Bh, float* Mo, int64_t M, int Cin, int Cout, const float* vbound, int nbound,
                               float b_scale, void* stream) {
-  if (!V || !Bh || !Mo || M < 0 || Cin <= 0 || Cout <= 0 || !vbound || nbound <= 0 || !(b_scale > 0.0f)) return EQA_ERR_INVALID_ARG;
-  if (M == 0) return EQA_OK;
-  const int F = eqa_fft48k5_frequencies();
-  const int64_t fm_bytes = ((M | 1) + 64) * 2 * (int64_t)std::max(Cin, Cout) * 4;
-  if (eqa_fft48k5_spectra3m_f16_bytes(Cin, Cout) == 0 || M > 0x3fffff || fm_bytes > 0x7fffffffLL || (int64_t)Cin * Cout * 6 * 2 > 0x7fffffffLL ||
-      (((uintptr_t)V | (uintptr_t)Bh | (uintptr_t)Mo) & 15) || (Cin / kStageK) % 2 != 0)
-    return EQA_ERR_UNSUPPORTED;
-  const int blocks = 256;
-  const int n_rb = (int)((M + kBlkM - 1) / kBlkM), n_cg = Cout / kBlkN;
-  constexpr int kLds = kABufs * a_stage_bytes(3);
-  if (!allow_dynamic_lds((const void*)fft_cgemm3m_bf16_block_kernel<3>, kLds)) return EQA_ERR_LAUNCH;
-  hipLaunchKernelGGL((fft_cgemm3m_bf16_block_kernel<3>), dim3(blocks), dim3(256), kLds, (hipStream_t)stream, V,
-                     static_cast<const uint16_t*>(Bh), Mo, (int)M, (int)eqa_fft48k5_tile_pitch(M), Cin, Cout, F, n_rb, n_cg, blocks / kXcd,
-                     vbound, nbound, b_scale);
-  return launch_status();
+  if (!vbound || nbound <= 0 || !(b_scale > 0.0f)) return EQA_ERR_INVALID_ARG;
+  const int st = check_contraction_args(V, Bh, Mo, M, Cin, Cout);
+  if (st != EQA_OK) return st == kNothingToDo ? EQA_OK : st;
+  // the block form only; its K loop runs stage pairs; one frequency of Bh: a descriptor range
+  if (Cout % kBlkN != 0 || (Cin / kStageK) % 2 != 0 || (int64_t)Cin * Cout * 6 * 2 > 0x7fffffffLL) return EQA_ERR_UNSUPPORTED;
+  return launch_block<3>(V, Bh, Mo, M, Cin, Cout, vbound, nbound, b_scale, stream);
 }
 
 }  // extern "C"

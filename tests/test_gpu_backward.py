@@ -378,7 +378,8 @@ def test_input_gradient_gather_equals_atomic_scatter(dev):
             lib.eqa_set_option(0, 0)
         assert torch.equal(g1, g1b)
         # the two kernels evaluate the sample coordinate with different FMA contraction: at 45 degrees and |coordinate| ~ 100
-        # that is ~1e-5 px, i.e. ~1e-5 of a bilinear weight (both are 7e-5 from the fp64 adjoint at 224 x 224)
+        # that is ~1e-5 px, i.e. ~1e-5 of a bilinear weight (each kernel's own distance from the fp64 adjoint, at 224 x 224 too,
+        # is held by tests/test_gpu_action_backward_fp64.py::test_input_gradient_matches_fp64)
         assert (g1 - g2).abs().max().item() <= 1e-4, (N, refl, C, H, W, (g1 - g2).abs().max().item())
         # adjoint identity <T x, g> == <x, T^* g>
         y = ops.group_action(src, gidx, th, fl, cmap, 0, (H, W), (0, 0))

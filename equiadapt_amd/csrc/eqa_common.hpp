@@ -17,6 +17,21 @@ namespace eqa {
 constexpr int kThreads = 256;  // block size of every kernel that does not say otherwise
 constexpr int kXcd = 8;        // MI355X: 8 XCDs, block b runs on XCD b % 8, each XCD has a private L2
 
+// XCD-aware work order: block b runs on XCD b % 8, and consecutive work items (the channel groups of one tile, neighbouring strips
+// of one image) go to one XCD, so that what they share is served by that XCD's L2.  Bijective for nwork % 8 != 0 as well.
+// r8 = nwork % 8, q8 = nwork / 8: a persistent kernel forms them once in front of its item loop and calls this form directly.
+// (By value and in this order: the generated code of every caller is what the formula written out in the kernel gave.)
+template <typename T>
+__device__ __forceinline__ T xcd_work_order(T v, T r8, T q8) {
+  const T xcd = v % kXcd;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + v / kXcd;
+}
+template <typename T>
+__device__ __forceinline__ T xcd_work_order(T v, T nwork) {
+  const T q8 = nwork / kXcd, r8 = nwork % kXcd;
+  return xcd_work_order<T>(v, r8, q8);
+}
+
 // window sums (pooling.hip) and the Winograd output transform that emits them directly (winograd.hip)
 constexpr int kMaxWinK = 10;                // (9: the reference tutorial's ESCNN canonicalizer, kernel_size = 9)
 constexpr int kWsMaxBorder = kMaxWinK - 1;  // k - 1 <= 9: register arrays of the kernels instantiated for 8 < k <= 10

@@ -1,5 +1,5 @@
-// libeqa_hip.so, part 8 -- 5x5 stride-1 group convolutions in inference as an overlap-save FFT convolution (I2a).
-// C ABI: include/eqa_hip.h.  Design notes: HISTORY.md section 3.4.
+// libeqa_hip.so, part 8 -- 5x5 stride-1 group convolutions in inference as an overlap-save FFT convolution (I2a): the transforms.
+// (fft_filter.hip holds the filter spectra and the filter gradient.)  C ABI: include/eqa_hip.h.  Design notes: HISTORY.md section 3.4.
 //
 // Winograd F(4x4,5x5) needs 4 multiplies per output and a 4x expansion of the activations (V, M: 8.1 GB each at the
 // headline shape); its library GEMM runs at the clock-limited fp32 roofline, so only fewer multiplies help.  A 48x48
@@ -55,6 +55,33 @@ __device__ __forceinline__ void fft_load_column(const float2* __restrict__ p, si
   }
 }
 
+// Tile m = (img * TY + ty) * TX + tx, and a work item of the fused kernels = (tile, group of 16 channels), the groups of a tile
+// consecutive:  const auto [grp, m, tx, ty, img] = fft_item(work, C / 16, TY, TX);
+struct FftTile {
+  int tx, ty;
+  size_t img;
+};
+__device__ __forceinline__ FftTile fft_tile(size_t m, int TY, int TX) {
+  return {(int)(m % TX), (int)((m / TX) % TY), m / ((size_t)TX * TY)};
+}
+struct FftItem {
+  int grp;
+  size_t m;
+  int tx, ty;
+  size_t img;
+};
+__device__ __forceinline__ FftItem fft_item(unsigned work, int ngrp, int TY, int TX) {
+  const int grp = work % ngrp;
+  const size_t m = work / ngrp;
+  const FftTile t = fft_tile(m, TY, TX);
+  return {grp, m, t.tx, t.ty, t.img};
+}
+
+// The LDS slabs of the fused kernels (kFusKxPitch, fft_common.inc): slab kx holds its column's 48 rows as [Re x 16 | Im x 16].
+// A row thread (y, cl) walks the slabs from fft_slab_row, a column thread (kx, cl) walks its slab from fft_slab_col.
+__device__ __forceinline__ float* fft_slab_row(float* lds, int y, int cl) { return lds + (y * 2) * kFusCh + cl; }
+__device__ __forceinline__ float* fft_slab_col(float* lds, int kx, int cl) { return lds + kx * kFusKxPitch + cl; }
+
 // (The two-pass kernels below take the tile's output size O = 49 - kernel size as a template argument: 44 for the 5 x 5 layers
 // -- where they are the fallback of the fused kernels further down -- and 46 / 42 / 40 for 3 x 3 / 7 x 7 / 9 x 9, which run
 // through them only: eqa_fft48_* entry points, round 4.)
@@ -94,9 +121,7 @@ __global__ __launch_bounds__(kThreads) void fft48_cols_fwd_kernel(const float* _
   if (c >= C) return;
   const int kx = blockIdx.x % kFftH;
   const size_t m = blockIdx.x / kFftH;  // (img * TY + ty) * TX + tx, img counted inside this chunk of images
-  const int tx = (int)(m % TX);
-  const int ty = (int)((m / TX) % TY);
-  const size_t img = m / ((size_t)TX * TY);
+  const auto [tx, ty, img] = fft_tile(m, TY, TX);
   const int y0 = O * ty;
   const int nvalid = min(win, H - y0);  // uniform
   const size_t pitch = (size_t)TX * kFftH * 2 * C;  // one image row of T
@@ -131,9 +156,7 @@ __global__ __launch_bounds__(kThreads) void fft48_cols_inv_kernel(const float* _
   if (c >= C) return;
   const int kx = blockIdx.x % kFftH;
   const size_t m = blockIdx.x / kFftH;
-  const int tx = (int)(m % TX);
-  const int ty = (int)((m / TX) % TY);
-  const size_t img = m / ((size_t)TX * TY);
+  const auto [tx, ty, img] = fft_tile(m, TY, TX);
   const float2* p = reinterpret_cast<const float2*>(Mo) + ((size_t)fft_f0(kx) * M + m0 + m) * (size_t)C + c;
   const size_t fpitch = (size_t)fft_fstep(kx) * M * C;
   float re[kFftN], im[kFftN], ore[kFftN], oim[kFftN];
@@ -297,10 +320,7 @@ __device__ unsigned long long g_fft_clock[32];  // [0..4] inverse, [8..12] forwa
 #define PIPE_CLOCK_WAIT(i) do { } while (0)
 #define PIPE_CLOCK_END(base) do { } while (0)
 #endif
-constexpr int kFusCh = 16;
-constexpr int kFusThreads = kFftN * kFusCh;                       // 768
-constexpr int kFusKxPitch = kFftN * 2 * kFusCh + kFusCh;          // floats per kx slab (+16: slabs start 16 banks apart)
-constexpr int kFusLds = kFftH * kFusKxPitch;                      // 38,800 floats = 155,200 bytes
+constexpr int kFusThreads = kFftN * kFusCh;                       // 768 (kFusCh and the LDS slabs: fft_common.inc)
 
 template <int O = kFftO>   // outputs per tile = the tile stride (44: 5 x 5 filters; 46 / 42 / 40: eqa_fft48_* for 3 / 7 / 9)
 __global__ __launch_bounds__(kFusThreads) void fft48_fwd_fused_kernel(const float* __restrict__ x, float* __restrict__ V,
@@ -309,16 +329,9 @@ __global__ __launch_bounds__(kFusThreads) void fft48_fwd_fused_kernel(const floa
                                                                       unsigned x_bytes, unsigned v_bytes, int x_grouped) {
   extern __shared__ float lds[];
   FFT_CLOCK_BEGIN();  // forward stamps: [8] loads, [9] row transform + LDS writes, [10] barrier, [11] LDS reads + column transform, [12] stores issued
-  // XCD-aware order: consecutive work items (the channel groups of one tile) on one XCD
-  const unsigned bid = blockIdx.x;
-  const unsigned q8 = nwork / kXcd, r8 = nwork % kXcd, xcd = bid % kXcd;
-  const unsigned work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / kXcd;
+  const unsigned work = xcd_work_order<unsigned>(blockIdx.x, nwork);  // consecutive work items (the channel groups of one tile) on one XCD
   const int ngrp = C / kFusCh;
-  const int grp = work % ngrp;
-  const size_t m = work / ngrp;  // (img * TY + ty) * TX + tx
-  const int tx = (int)(m % TX);
-  const int ty = (int)((m / TX) % TY);
-  const size_t img = m / ((size_t)TX * TY);
+  const auto [grp, m, tx, ty, img] = fft_item(work, ngrp, TY, TX);
   const int cl = threadIdx.x % kFusCh;
   const int c = grp * kFusCh + cl;
   {
@@ -361,7 +374,7 @@ __global__ __launch_bounds__(kFusThreads) void fft48_fwd_fused_kernel(const floa
     }
     FFT_CLOCK_USE(re[0], 8);
     fft48_r2c(re, ore, oim);
-    float* o = lds + (y * 2) * kFusCh + cl;
+    float* o = fft_slab_row(lds, y, cl);
 #pragma unroll
     for (int k = 0; k < kFftH; ++k) {
       o[k * kFusKxPitch] = ore[k];
@@ -373,7 +386,7 @@ __global__ __launch_bounds__(kFusThreads) void fft48_fwd_fused_kernel(const floa
   FFT_CLOCK(10);
   if (threadIdx.x < kFftH * kFusCh) {
     const int kx = threadIdx.x / kFusCh;
-    const float* q = lds + kx * kFusKxPitch + cl;
+    const float* q = fft_slab_col(lds, kx, cl);
     float re[kFftN], im[kFftN], ore[kFftN], oim[kFftN];
 #pragma unroll
     for (int i = 0; i < kFftN; ++i) {
@@ -439,11 +452,7 @@ __global__ __launch_bounds__(kFwdPipeThreads) void fft48_fwd_pipe_kernel(const f
   extern __shared__ float lds[];
   const unsigned nblk = gridDim.x;               // a multiple of the XCD count (or < 8): virtual block v runs on XCD v % 8
   const int ngrp = C / kFusCh;
-  const unsigned q8 = nwork / kXcd, r8 = nwork % kXcd;
-  auto work_of = [&](unsigned v) {
-    const unsigned xcd = v % kXcd;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + v / kXcd;
-  };
+  const unsigned q8 = nwork / kXcd, r8 = nwork % kXcd;   // formed once, in front of the role split and the item loops
   if (threadIdx.x < kFwdRowT) {
     // ---------------------------------------------------------------- row waves
     const int ry = threadIdx.x / kFusCh, cl = threadIdx.x % kFusCh;
@@ -453,7 +462,7 @@ __global__ __launch_bounds__(kFwdPipeThreads) void fft48_fwd_pipe_kernel(const f
     // 0xffffe000 + the largest scalar offset does not wrap, and the launcher keeps the map below it)
 #define EQA_FWD_ISSUE(v_)                                                                                                     \
   do {                                                                                                                        \
-    const unsigned work_ = work_of(v_);                                                                                       \
+    const unsigned work_ = xcd_work_order(v_, r8, q8);                                                                        \
     const unsigned grp_ = work_ % ngrp, m_ = work_ / ngrp;                                                                    \
     const unsigned tx_ = m_ % TX, ty_ = (m_ / TX) % TY, img_ = m_ / (TX * TY);                                                \
     const int gy0_ = kFftO * (int)ty_ + ry, gy1_ = gy0_ + 24;                                                                 \
@@ -468,8 +477,8 @@ __global__ __launch_bounds__(kFwdPipeThreads) void fft48_fwd_pipe_kernel(const f
   } while (0)
     unsigned v = blockIdx.x;
     EQA_FWD_ISSUE(v);
-    float* const o0 = lds + (ry * 2) * kFusCh + cl;
-    float* const o1 = lds + ((ry + 24) * 2) * kFusCh + cl;
+    float* const o0 = fft_slab_row(lds, ry, cl);
+    float* const o1 = fft_slab_row(lds, ry + 24, cl);
     for (; v < nwork; v += nblk) {
       float ore[kFftH], oim[kFftH];
       fft48_r2c(r0, ore, oim);
@@ -498,14 +507,14 @@ __global__ __launch_bounds__(kFwdPipeThreads) void fft48_fwd_pipe_kernel(const f
   const int kc = t / kFusCh, cl = t % kFusCh;
   const bool packed = kc == kFftInner;                   // the last column task: kx = 0 and kx = 24 in one transform
   const int kx = packed ? 0 : kc + 1;
-  const float* const qre = lds + kx * kFusKxPitch + cl;
+  const float* const qre = fft_slab_col(lds, kx, cl);
   // imaginary parts: the column's own (interior columns); the REAL parts of column 24 (packed task)
-  const float* const qim = packed ? lds + (kFftH - 1) * kFusKxPitch + cl : qre + kFusCh;
+  const float* const qim = packed ? fft_slab_col(lds, kFftH - 1, cl) : qre + kFusCh;
   const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(V, 0, v_bytes, 0x00020000);
   const unsigned step_in = (unsigned)((size_t)kFftInner * M * 2 * C * 4);       // interior columns: 23 frequencies per ky
   const unsigned step_ed = (unsigned)((size_t)2 * M * 2 * C * 4);               // edge columns: 2 per ky
   for (unsigned v = blockIdx.x; v < nwork; v += nblk) {
-    const unsigned work = work_of(v);
+    const unsigned work = xcd_work_order(v, r8, q8);
     const unsigned grp = work % ngrp, m = work / ngrp;
     float re[kFftN], im[kFftN], ore[kFftN], oim[kFftN];
     __syncthreads();                                     // A
@@ -613,26 +622,15 @@ __global__ __launch_bounds__(kFftN * CH) void fft48_inv_fused_kernel(const float
   static_assert(NB == 0 || O == kFftO, "the window-sum epilogue is written for 44-output tiles");
   extern __shared__ float lds[];
   FFT_CLOCK_BEGIN();
-  constexpr int kPitch = kFftN * 2 * CH + CH;  // floats per kx slab
-  const unsigned bid = blockIdx.x;
-  const unsigned q8 = nwork / kXcd, r8 = nwork % kXcd, xcd = bid % kXcd;
-  const unsigned work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / kXcd;
+  static_assert(CH == kFusCh, "the LDS slabs are laid out for 16 channels per block");
+  const unsigned work = xcd_work_order<unsigned>(blockIdx.x, nwork);
   const int ngrp = C / CH;
-  const int grp = work % ngrp;
-  const size_t m = work / ngrp;
-  const int tx = (int)(m % TX);
-  const int ty = (int)((m / TX) % TY);
-  const size_t img = m / ((size_t)TX * TY);
+  const auto [grp, m, tx, ty, img] = fft_item(work, ngrp, TY, TX);
   const int cl = threadIdx.x % CH;
   const int c = grp * CH + cl;
   if (threadIdx.x < kFftH * CH) {
     const int kx = threadIdx.x / CH;
-#ifdef EQA_FFT_SAMETILE  // experiment: every block reads tile 0 (L2-resident) -- the kernel without its HBM wait
-    const size_t m_ld = 0;
-#else
-    const size_t m_ld = m;
-#endif
-    const float2* p = reinterpret_cast<const float2*>(Mo) + ((size_t)fft_f0(kx) * M + m_ld) * (size_t)C + c;
+    const float2* p = reinterpret_cast<const float2*>(Mo) + ((size_t)fft_f0(kx) * M + m) * (size_t)C + c;
     const size_t fpitch = (size_t)fft_fstep(kx) * M * C;
     float re[kFftN], im[kFftN], ore[kFftN], oim[kFftN];
     const bool edge = fft_edge(kx);
@@ -641,7 +639,7 @@ __global__ __launch_bounds__(kFftN * CH) void fft48_inv_fused_kernel(const float
       // 23 * M * C complex numbers -> buffer loads with that step as a SCALAR offset, no vector address arithmetic at all
       // (mo_bytes = 0: the spectra do not fit a 32-bit offset, pointer arithmetic as in the edge waves)
       const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Mo), 0, mo_bytes, 0x00020000);
-      const unsigned voff = (unsigned)((((size_t)fft_f0(kx) * M + m_ld) * (size_t)C + c) * 8);
+      const unsigned voff = (unsigned)((((size_t)fft_f0(kx) * M + m) * (size_t)C + c) * 8);
       const unsigned step = (unsigned)(kFftInner * M * (size_t)C * 8);
 #pragma unroll
       for (int ky = 0; ky < kFftN; ++ky) {
@@ -654,7 +652,7 @@ __global__ __launch_bounds__(kFftN * CH) void fft48_inv_fused_kernel(const float
     }
     FFT_CLOCK_LOADS();
     fft48(im, re, oim, ore);
-    float* q = lds + kx * kPitch + cl;
+    float* q = fft_slab_col(lds, kx, cl);
 #pragma unroll
     for (int i = 0; i < O; ++i) {  // rows O..47: the circular wrap-around
       q[(i * 2) * CH] = ore[i];
@@ -672,12 +670,12 @@ __global__ __launch_bounds__(kFftN * CH) void fft48_inv_fused_kernel(const float
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0.0f;
   if (valid) {
-    const float* q = lds + (y * 2) * CH + cl;
+    const float* q = fft_slab_row(lds, y, cl);
     float re[kFftH], im[kFftH], ore[kFftN];
 #pragma unroll
     for (int k = 0; k < kFftH; ++k) {
-      re[k] = q[k * kPitch];
-      im[k] = q[k * kPitch + CH];
+      re[k] = q[k * kFusKxPitch];
+      im[k] = q[k * kFusKxPitch + CH];
     }
     // the bias rides on the row's DC bin: the (unnormalised) inverse adds re[0] to every output
     const float b = bias ? bias[c] : 0.0f;
@@ -752,6 +750,7 @@ __global__ __launch_bounds__(kFftN * CH) void fft48_inv_fused_kernel(const float
 // 128 and the producer loop spills its incoming column).
 constexpr int kPipeProd = 7 * 64, kPipeCons = 5 * 64, kPipeThreads = kPipeProd + kPipeCons;
 constexpr int kPipePasses = (kFftO * 16 + kPipeCons - 1) / kPipeCons;  // 20 rows of 16 channels per pass: 3 passes (20 + 20 + 4)
+constexpr int kPipeEarly = 16;   // loads of the next item issued BEFORE barrier A (see the producer loop)
 
 // STATS (NB == 0, training: an InnerBatchNorm follows): every consumer thread also sums the values (and their squares) it stores
 // for its channel; per item, a consumer wave's 4 rows are folded by shuffles and its 16 lanes write one fp64 partial row
@@ -764,16 +763,12 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
                                                                      double* __restrict__ stats) {
   static_assert(!STATS || NB == 0, "statistics are taken of the full map");
   extern __shared__ float lds[];
-  constexpr int kPitch = kFftN * 2 * CH + CH;  // floats per kx slab
+  static_assert(CH == kFusCh, "the LDS slabs are laid out for 16 channels per block");
   constexpr int NV = 1 + 2 * NB;
   constexpr int kPassRows = kPipeCons / CH;      // 20 rows per consumer pass
   const unsigned nblk = gridDim.x;               // a multiple of the XCD count (or < 8): virtual block v runs on XCD v % 8 = blockIdx % 8
   const int ngrp = C / CH;
-  const unsigned q8 = nwork / kXcd, r8 = nwork % kXcd;
-  auto work_of = [&](unsigned v) {
-    const unsigned xcd = v % kXcd;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + v / kXcd;
-  };
+  const unsigned q8 = nwork / kXcd, r8 = nwork % kXcd;   // formed once, in front of the role split and the item loops
   if (threadIdx.x < kPipeProd) {
     // ---------------------------------------------------------------- producers
     // the 48 idle lanes of the seventh wave duplicate its column kx = 24 (same loads, same values to the same LDS words): the
@@ -791,13 +786,10 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
     float re[kFftN], im[kFftN];
     // lstep is made opaque at every issue: otherwise its 48 multiples are hoisted out of the item loop as loop invariants and
     // the incoming column is spilled to make room for them
-#ifndef EQA_PIPE_EARLY
-#define EQA_PIPE_EARLY 16   // loads of the next item issued BEFORE barrier A (see the loop below)
-#endif
 #define EQA_PIPE_ISSUE_RANGE(v_, K0_, K1_)                                                                                    \
   do {                                                                                                                       \
     asm volatile("" : "+v"(lstep));                                                                                          \
-    const unsigned work_ = work_of(v_);                                                                                      \
+    const unsigned work_ = xcd_work_order(v_, r8, q8);                                                                       \
     const unsigned item_ = (unsigned)(((size_t)(work_ / ngrp) * C + (size_t)(work_ % ngrp) * CH) * 8);                       \
     const unsigned base_ = (v_) < nwork ? col0 + item_ : 0xfffffff0u;                                                        \
     _Pragma("unroll") for (int ky = (K0_); ky < (K1_); ++ky) {                                                               \
@@ -816,7 +808,7 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
 #define EQA_PIPE_ISSUE(v_) EQA_PIPE_ISSUE_RANGE(v_, 0, kFftN)
     unsigned v = blockIdx.x;
     EQA_PIPE_ISSUE(v);
-    float* const q = lds + kx * kPitch + cl;
+    float* const q = fft_slab_col(lds, kx, cl);
     PIPE_CLOCK_BEGIN(0);  // producer stamps: [16] wait for the loads, [17] column transform + LDS writes, [18] wait at A, [19] issue, [20] wait at B
     for (; v < nwork; v += nblk) {
       PIPE_CLOCK_WAIT(0);
@@ -829,16 +821,16 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
       }
       PIPE_CLOCK(1);
       // The column's registers are free as soon as its transform is in LDS, and the producers used to wait ~2.4 k cycles at A for
-      // the consumers' epilogue of the previous item with nothing in flight: the first EQA_PIPE_EARLY loads of the next item go out
+      // the consumers' epilogue of the previous item with nothing in flight: the first kPipeEarly loads of the next item go out
       // in that window (more would delay the producers' arrival at A -- the memory pipe throttles the issue -- and the consumers
       // with it), the rest behind A as before.
       __builtin_amdgcn_sched_barrier(0);
-      EQA_PIPE_ISSUE_RANGE(v + nblk, 0, EQA_PIPE_EARLY);
+      EQA_PIPE_ISSUE_RANGE(v + nblk, 0, kPipeEarly);
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       __syncthreads();                                   // A: the item's column transforms are in LDS
       PIPE_CLOCK(2);
-      EQA_PIPE_ISSUE_RANGE(v + nblk, EQA_PIPE_EARLY, kFftN);
+      EQA_PIPE_ISSUE_RANGE(v + nblk, kPipeEarly, kFftN);
       asm volatile("" ::: "memory");                     // the loads stay on this side of the barrier
       __builtin_amdgcn_sched_barrier(0);
       PIPE_CLOCK(3);
@@ -856,12 +848,8 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
   const unsigned cons_wave = __builtin_amdgcn_readfirstlane((unsigned)t >> 6);   // wave-uniform: lives in a scalar register
   PIPE_CLOCK_BEGIN(kPipeProd);  // consumer stamps: [24] wait at A, [25] passes before the last LDS read, [26] wait at B, [27] last pass + pieces
   for (unsigned v = blockIdx.x; v < nwork; v += nblk) {
-    const unsigned work = work_of(v);
-    const int grp = work % ngrp;
-    const size_t m = work / ngrp;
-    const int tx = (int)(m % TX);
-    const int ty = (int)((m / TX) % TY);
-    const size_t img = m / ((size_t)TX * TY);
+    const unsigned work = xcd_work_order(v, r8, q8);
+    const auto [grp, m, tx, ty, img] = fft_item(work, ngrp, TY, TX);
     const int c = grp * CH + cl;
     const float b = bias ? bias[c] : 0.0f;
     const int x0 = kFftO * tx;
@@ -880,11 +868,11 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
       const bool valid = y < kFftO && gy < OH;
       float re[kFftH], im[kFftH], ore[kFftN];
       if (valid) {
-        const float* q = lds + (y * 2) * CH + cl;
+        const float* q = fft_slab_row(lds, y, cl);
 #pragma unroll
         for (int k = 0; k < kFftH; ++k) {
-          re[k] = q[k * kPitch];
-          im[k] = q[k * kPitch + CH];
+          re[k] = q[k * kFusKxPitch];
+          im[k] = q[k * kFusKxPitch + CH];
         }
       }
       if (pass == kPipePasses - 1) {
@@ -956,703 +944,302 @@ __global__ __launch_bounds__(kPipeThreads) void fft48_inv_pipe_kernel(const floa
   PIPE_CLOCK_END(24);
 }
 
-// Filter spectra for the batched GEMM: bank (Cout, Cin, 5, 5) -> B (F, 2 Cin, 2 Cout), B[f] = [[Br, Bi], [-Bi, Br]] with
-// Br + i Bi = conj(FFT48x48(filter))[ky][kx] / 48^2 = sum_{u,v} w[u][v] (cos t + i sin t) / 2304, t = 2 pi (ky u + kx v) / 48.
-// Rows follow the rows of V ([Re x G | Im x G] per group of G input channels), columns the rows of Mo (interleaved complex).
-// One thread per (ci, co) keeps its 25 taps in registers and walks the frequencies (fp64 accumulation, twiddles from a
-// 48-entry table): 0.3 ms for 256 x 256 filters, against 13.6 ms for the same through torch.fft + concatenations -- cheap
-// enough to run every training step.
-// `sgn` = +1: the correlation form above (forward pass); -1: FFT(filter) itself, for the convolution of the input gradient.
-template <int KS>
-__global__ __launch_bounds__(kThreads) void fft48_filter_spectra_kernel(const float* __restrict__ bank, float* __restrict__ B, int Cout,
-                                                                       int Cin, int G, float sgn) {
-  __shared__ double tw_c[kFftN], tw_s[kFftN];
-  if (threadIdx.x < kFftN) {
-    const double t = 6.283185307179586476925286766559 * threadIdx.x / kFftN;
-    tw_c[threadIdx.x] = cos(t);
-    tw_s[threadIdx.x] = sin(t);
-  }
-  __syncthreads();
-  const int co = blockIdx.y * kThreads + threadIdx.x;
-  const int ci = blockIdx.x;
-  if (co >= Cout) return;
-  double w[KS * KS];
-#pragma unroll
-  for (int i = 0; i < KS * KS; ++i) w[i] = bank[((size_t)co * Cin + ci) * (KS * KS) + i];
-  const int r0 = (ci / G) * 2 * G + ci % G, r1 = r0 + G;
-  const size_t fstride = (size_t)2 * Cin * 2 * Cout;
-  float2* o0 = reinterpret_cast<float2*>(B + (size_t)r0 * 2 * Cout) + co;
-  float2* o1 = reinterpret_cast<float2*>(B + (size_t)r1 * 2 * Cout) + co;
-  constexpr double inv = 1.0 / (kFftN * kFftN);
-  // separable: S_u(kx) = sum_v w[u][v] e^{i t kx v} once per kx, then sum_u e^{i t ky u} S_u for the 48 ky
-  // (25 x (50 + 48 x 20) multiply-adds per filter instead of 1200 x 50 in the direct form, and a fifth of the table look-ups)
-  for (int kx = 0; kx < kFftH; ++kx) {
-    double sr[KS], si[KS];
-#pragma unroll
-    for (int u = 0; u < KS; ++u) {
-      sr[u] = 0.0;
-      si[u] = 0.0;
-#pragma unroll
-      for (int v = 0; v < KS; ++v) {
-        const int t = (kx * v) % kFftN;
-        sr[u] += w[u * KS + v] * tw_c[t];
-        si[u] += w[u * KS + v] * tw_s[t];
-      }
-    }
-    const int nky = fft_nky(kx), f0 = fft_f0(kx), fstep = fft_fstep(kx);
-    for (int ky = 0; ky < nky; ++ky) {
-      double br = 0.0, bi = 0.0;
-#pragma unroll
-      for (int u = 0; u < KS; ++u) {
-        const int t = (ky * u) % kFftN;
-        const double c = tw_c[t], sn = tw_s[t];
-        br += c * sr[u] - sn * si[u];
-        bi += c * si[u] + sn * sr[u];
-      }
-      const float fr = (float)(br * inv), fi = sgn * (float)(bi * inv);
-      const size_t f = (size_t)(f0 + ky * fstep) * (fstride / 2);  // in float2
-      o0[f] = make_float2(fr, fi);
-      o1[f] = make_float2(-fi, fr);
-    }
-  }
+// ------------------------------------------------------------------------------------------------------------------------------
+// The launch plan.  FftK<KS> is the one place that launches a transform kernel, for any odd kernel size 3 .. 9 (O = 49 - KS outputs
+// per tile: 46 / 44 / 42 / 40).  The fused kernels run where C % 16 == 0, the two-pass kernels otherwise, under EQA_FFT_TWO_PASS
+// and for the input gradient.  What only the eqa_fft48k5_* entry points ask for -- the grouped input layout, the opt-in forward
+// pipeline, the pipelined inverse with its window-sum (NB) and statistics forms -- is an explicit option: eqa_fft48_*(ksize = 5)
+// takes none of them.  The reference's kernel_size is a free constructor argument (escnn_networks.py:19-44): its tutorial trains
+// k = 9, its own test k = 3.  The multiply count per output falls with k^2: 1154 x 3 real products per 40 x 40 outputs and channel
+// pair at k = 9 against 81 in the direct form.  The per-frequency channel contraction is k-independent: eqa_fft48k5_cgemm3m /
+// _wgrad3m / torch.bmm on buffers of eqa_fft48k5_tile_pitch rows.
+// ------------------------------------------------------------------------------------------------------------------------------
+
+bool fft_two_pass() {  // ablation switch: the unfused passes
+  static const bool on = getenv("EQA_FFT_TWO_PASS") != nullptr;
+  return on;
+}
+bool fft_inv_pipe_on() {  // EQA_FFT_INV_PIPE=0: one block per work item
+  static const bool on = []() { const char* e = getenv("EQA_FFT_INV_PIPE"); return !(e && e[0] == '0'); }();
+  return on;
 }
 
-// The same filter spectra in the operand order of the hand-written 3-multiplication complex GEMM (cgemm3m.hip):
-// B3 (F, S = Cin/16, Cout/32, 3 [Br | Bi | Br + Bi], 2 [b], 64 [lane = 32 h + j], 4 [t]) with k = 16 s + 8 b + 4 h + t the input
-// channel and 32 c + j the output channel: a wave's B fragment of one MFMA k-block is one contiguous 1 KB run.  Thread = (output
-// channel, 4 consecutive input channels = t) for one kx: three 16-byte stores per frequency, fully coalesced over the lanes.
-// Br + Bi is the correctly rounded sum of the two STORED floats (fp64 add of the rounded values), so that
-// Ci = (Ar + Ai)(Br + Bi) - Ar Br - Ai Bi cancels against exactly the Br, Bi the other two products see.
-template <int KS>
-__global__ __launch_bounds__(kThreads) void fft48_filter_spectra3m_kernel(const float* __restrict__ bank, float* __restrict__ B3, int Cout,
-                                                                         int Cin, float sgn) {
-  __shared__ double tw_c[kFftN], tw_s[kFftN];
-  if (threadIdx.x < kFftN) {
-    const double t = 6.283185307179586476925286766559 * threadIdx.x / kFftN;
-    tw_c[threadIdx.x] = cos(t);
-    tw_s[threadIdx.x] = sin(t);
-  }
-  __syncthreads();
-  const int co = blockIdx.y * kThreads + threadIdx.x;
-  const int cq = blockIdx.x;                      // quad of input channels 4 cq .. 4 cq + 3
-  const int kx = blockIdx.z;
-  if (co >= Cout) return;
-  constexpr double inv = 1.0 / (kFftN * kFftN);
-  // S_u(kx) = sum_v w[u][v] e^{i t kx v} for the 4 filters of this thread
-  double sr[4][KS], si[4][KS];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float* w = bank + ((size_t)co * Cin + 4 * cq + c) * (KS * KS);
-#pragma unroll
-    for (int u = 0; u < KS; ++u) {
-      sr[c][u] = 0.0;
-      si[c][u] = 0.0;
-#pragma unroll
-      for (int v = 0; v < KS; ++v) {
-        const int t = (kx * v) % kFftN;
-        const double wv = w[u * KS + v];
-        sr[c][u] += wv * tw_c[t];
-        si[c][u] += wv * tw_s[t];
-      }
-    }
-  }
-  const int S = Cin / 16;
-  const int k0 = 4 * cq, s = k0 / 16, b = (k0 % 16) / 8, h = (k0 % 8) / 4;
-  const int c32 = co / 32, lane = 32 * h + (co % 32);
-  const size_t per_f = (size_t)Cin * Cout * 3;
-  float4* o = reinterpret_cast<float4*>(B3 + (((((size_t)s * (Cout / 32) + c32) * 3) * 2 + b) * 64 + lane) * 4);   // part 0
-  const size_t part = (size_t)2 * 64;             // float4 between the parts
-  (void)S;
-  const int nky = fft_nky(kx), f0 = fft_f0(kx), fstep = fft_fstep(kx);
-  for (int ky = 0; ky < nky; ++ky) {
-    float fr[4], fi[4], fs[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      double br = 0.0, bi = 0.0;
-#pragma unroll
-      for (int u = 0; u < KS; ++u) {
-        const int t = (ky * u) % kFftN;
-        const double cs = tw_c[t], sn = tw_s[t];
-        br += cs * sr[c][u] - sn * si[c][u];
-        bi += cs * si[c][u] + sn * sr[c][u];
-      }
-      fr[c] = (float)(br * inv);
-      fi[c] = sgn * (float)(bi * inv);
-      fs[c] = (float)((double)fr[c] + (double)fi[c]);
-    }
-    float4* of = o + (size_t)(f0 + ky * fstep) * (per_f / 4);
-    of[0] = make_float4(fr[0], fr[1], fr[2], fr[3]);
-    of[part] = make_float4(fi[0], fi[1], fi[2], fi[3]);
-    of[2 * part] = make_float4(fs[0], fs[1], fs[2], fs[3]);
-  }
-}
+// Tiles of a map and what the launches derive from them.
+struct FftTiles {
+  int TY, TX;
+  size_t M, pitch;
+  FftTiles(int nimg, int TY_, int TX_) : TY(TY_), TX(TX_), M((size_t)nimg * TY_ * TX_), pitch(fft_pitch(M)) {}
+  // every block index fits 31 bits; row_blocks: what the row pass puts into grid.x
+  bool in_range(size_t row_blocks) const { return row_blocks <= 0x7fffffffULL && M * kFftH <= 0x7fffffffULL; }
+  // the fused kernels: one work item per (tile, 16 channels)
+  bool fusable(int C) const { return C % kFusCh == 0 && M * (C / kFusCh) <= 0x7fffffffULL && !fft_two_pass(); }
+  unsigned nwork(int C) const { return (unsigned)(M * (C / kFusCh)); }
+  size_t spectra_bytes(int C) const { return (size_t)kFftF * pitch * 2 * C * sizeof(float); }   // V, Mo, G
+};
+// size of a buffer for a 32-bit buffer descriptor; 0 tells the kernel that it does not fit (pointer arithmetic instead)
+unsigned fft_desc_bytes(size_t bytes) { return bytes <= 0xfffffff0ULL ? (unsigned)bytes : 0u; }
 
-// Filter gradient in the frequency domain (training).  With G = the spectra of the output-gradient tiles (44 x 44, zero-padded
-// to 48: eqa_fft48k5_grad_transform) and V those of the input tiles, D[f] = V[f]^T . G[f] (real form, one batched GEMM over
-// the tiles) holds  Dr = D[re ci][re co] + D[im ci][im co],  Di = D[im ci][re co] - D[re ci][im co]  of  X_f^T conj(G_f), and
-//   dW[co][ci][u][v] = 1/48^2 sum_f wgt(f) (cos t Dr - sin t Di),  t = 2 pi (ky u + kx v) / 48,
-// wgt = 2 for the stored frequencies whose conjugate partner is not stored, 1 for the self-conjugate ones -- the correlation theorem; no
-// wrap-around because a 44-wide gradient tile shifted by up to 4 stays inside the 48-wide input tile.
-// PACKED: D3 (F, Cin, 2, Cout) as eqa_fft48k5_wgrad3m writes it -- Dr | Di per input channel, plain channel order.
-template <bool PACKED, int KS>
-__global__ __launch_bounds__(kThreads) void fft48_filter_grad_kernel(const float* __restrict__ D, float* __restrict__ dbank, int Cout,
-                                                                    int Cin, int Gin, int Gout) {
-  __shared__ double tw_c[kFftN], tw_s[kFftN];
-  if (threadIdx.x < kFftN) {
-    const double t = 6.283185307179586476925286766559 * threadIdx.x / kFftN;
-    tw_c[threadIdx.x] = cos(t);
-    tw_s[threadIdx.x] = sin(t);
-  }
-  __syncthreads();
-  const int co = blockIdx.y * kThreads + threadIdx.x;
-  const int ci = blockIdx.x;
-  if (co >= Cout) return;
-  const int r0 = (ci / Gin) * 2 * Gin + ci % Gin, r1 = r0 + Gin;
-  const int c0 = (co / Gout) * 2 * Gout + co % Gout, c1 = c0 + Gout;
-  const size_t ld = (size_t)2 * Cout, fstride = (size_t)2 * Cin * (PACKED ? (size_t)Cout : ld);
-  const size_t p_dr = ((size_t)2 * ci) * Cout + co, p_di = p_dr + Cout;   // PACKED
-  double acc[KS * KS];
-#pragma unroll
-  for (int i = 0; i < KS * KS; ++i) acc[i] = 0.0;
-  // separable, like the spectra kernel: A_u(kx) = sum_ky e^{i t ky u} D(ky, kx), then dW[u][v] += Re(e^{i t kx v} A_u(kx))
-  for (int kx = 0; kx < kFftH; ++kx) {
-    const bool edge = fft_edge(kx);
-    const int nky = fft_nky(kx), f0 = fft_f0(kx), fstep = fft_fstep(kx);
-    double ar[KS], ai[KS];
-#pragma unroll
-    for (int u = 0; u < KS; ++u) { ar[u] = 0.0; ai[u] = 0.0; }
-    // one block per CU and one thread per filter: the loop is a chain of round trips unless several frequencies are requested
-    // together (0.56 ms for 1.26 GB at one ky per trip).  Eight per trip; the sums run over ky in the same order.
-    constexpr int kKyBatch = 8;
-    for (int ky0 = 0; ky0 < nky; ky0 += kKyBatch) {
-      float q[kKyBatch][PACKED ? 2 : 4];
-#pragma unroll
-      for (int b = 0; b < kKyBatch; ++b) {
-        const float* d = D + (size_t)(f0 + min(ky0 + b, nky - 1) * fstep) * fstride;
-        if (PACKED) {
-          q[b][0] = d[p_dr];
-          q[b][1] = d[p_di];
-        } else {
-          q[b][0] = d[r0 * ld + c0];
-          q[b][1] = d[r1 * ld + c1];
-          q[b][PACKED ? 0 : 2] = d[r1 * ld + c0];
-          q[b][PACKED ? 1 : 3] = d[r0 * ld + c1];
-        }
-      }
-#pragma unroll
-      for (int b = 0; b < kKyBatch; ++b) {
-        const int ky = ky0 + b;
-        if (ky < nky) {
-          // weight 2 for every stored frequency whose conjugate partner is not stored; 1 for the four self-conjugate ones
-          const double wgt = (edge && (ky == 0 || ky == kFftH - 1)) ? 1.0 : 2.0;
-          const double dr = PACKED ? wgt * (double)q[b][0] : wgt * ((double)q[b][0] + (double)q[b][1]);
-          const double di = PACKED ? wgt * (double)q[b][1] : wgt * ((double)q[b][PACKED ? 0 : 2] - (double)q[b][PACKED ? 1 : 3]);
-#pragma unroll
-          for (int u = 0; u < KS; ++u) {
-            const int t = (ky * u) % kFftN;
-            const double c = tw_c[t], sn = tw_s[t];
-            ar[u] += c * dr - sn * di;
-            ai[u] += c * di + sn * dr;
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < KS; ++u)
-#pragma unroll
-      for (int v = 0; v < KS; ++v) {
-        const int t = (kx * v) % kFftN;
-        acc[u * KS + v] += tw_c[t] * ar[u] - tw_s[t] * ai[u];
-      }
-  }
-  constexpr double inv = 1.0 / (kFftN * kFftN);
-  float* o = dbank + ((size_t)co * Cin + ci) * (KS * KS);
-#pragma unroll
-  for (int i = 0; i < KS * KS; ++i) o[i] = (float)(acc[i] * inv);
-}
-
-// The same reduction with one thread per (ci, co, filter ROW u = blockIdx.z): KS x the blocks and 1 / KS of the accumulators.  With
-// few channels the kernel above is a handful of blocks of long serial threads (64 x 64 channels at k = 9: 64 blocks, 81 fp64
-// accumulators per thread, 0.52 ms -- 5 % of the reference tutorial's training step); the KS rows re-read D from L2.  Same sums
-// in the same order per element, so both forms give identical filters.
-template <bool PACKED, int KS>
-__global__ __launch_bounds__(kThreads) void fft48_filter_grad_rows_kernel(const float* __restrict__ D, float* __restrict__ dbank, int Cout,
-                                                                         int Cin, int Gin, int Gout) {
-  __shared__ double tw_c[kFftN], tw_s[kFftN];
-  if (threadIdx.x < kFftN) {
-    const double t = 6.283185307179586476925286766559 * threadIdx.x / kFftN;
-    tw_c[threadIdx.x] = cos(t);
-    tw_s[threadIdx.x] = sin(t);
-  }
-  __syncthreads();
-  const int co = blockIdx.y * kThreads + threadIdx.x;
-  const int ci = blockIdx.x;
-  const int u = blockIdx.z;
-  if (co >= Cout) return;
-  const int r0 = (ci / Gin) * 2 * Gin + ci % Gin, r1 = r0 + Gin;
-  const int c0 = (co / Gout) * 2 * Gout + co % Gout, c1 = c0 + Gout;
-  const size_t ld = (size_t)2 * Cout, fstride = (size_t)2 * Cin * (PACKED ? (size_t)Cout : ld);
-  const size_t p_dr = ((size_t)2 * ci) * Cout + co, p_di = p_dr + Cout;
-  double acc[KS];
-#pragma unroll
-  for (int v = 0; v < KS; ++v) acc[v] = 0.0;
-  for (int kx = 0; kx < kFftH; ++kx) {
-    const bool edge = fft_edge(kx);
-    const int nky = fft_nky(kx), f0 = fft_f0(kx), fstep = fft_fstep(kx);
-    double ar = 0.0, ai = 0.0;
-    constexpr int kKyBatch = 8;
-    for (int ky0 = 0; ky0 < nky; ky0 += kKyBatch) {
-      float q[kKyBatch][PACKED ? 2 : 4];
-#pragma unroll
-      for (int b = 0; b < kKyBatch; ++b) {
-        const float* d = D + (size_t)(f0 + min(ky0 + b, nky - 1) * fstep) * fstride;
-        if (PACKED) {
-          q[b][0] = d[p_dr];
-          q[b][1] = d[p_di];
-        } else {
-          q[b][0] = d[r0 * ld + c0];
-          q[b][1] = d[r1 * ld + c1];
-          q[b][PACKED ? 0 : 2] = d[r1 * ld + c0];
-          q[b][PACKED ? 1 : 3] = d[r0 * ld + c1];
-        }
-      }
-#pragma unroll
-      for (int b = 0; b < kKyBatch; ++b) {
-        const int ky = ky0 + b;
-        if (ky < nky) {
-          const double wgt = (edge && (ky == 0 || ky == kFftH - 1)) ? 1.0 : 2.0;
-          const double dr = PACKED ? wgt * (double)q[b][0] : wgt * ((double)q[b][0] + (double)q[b][1]);
-          const double di = PACKED ? wgt * (double)q[b][1] : wgt * ((double)q[b][PACKED ? 0 : 2] - (double)q[b][PACKED ? 1 : 3]);
-          const int t = (ky * u) % kFftN;
-          const double c = tw_c[t], sn = tw_s[t];
-          ar += c * dr - sn * di;
-          ai += c * di + sn * dr;
-        }
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < KS; ++v) {
-      const int t = (kx * v) % kFftN;
-      acc[v] += tw_c[t] * ar - tw_s[t] * ai;
-    }
-  }
-  constexpr double inv = 1.0 / (kFftN * kFftN);
-  float* o = dbank + ((size_t)co * Cin + ci) * (KS * KS) + u * KS;
-#pragma unroll
-  for (int v = 0; v < KS; ++v) o[v] = (float)(acc[v] * inv);
-}
-
-int fft_dims_ok(int nimg, int H, int W, int C) { return nimg >= 0 && H >= 5 && W >= 5 && C > 0; }
-
-#ifndef EQA_FFT_INV_CH
-#define EQA_FFT_INV_CH 16
-#endif
-constexpr int kInvCh = EQA_FFT_INV_CH;  // channels per block of the fused inverse (8, two blocks per CU: 1.54 ms; 16: 1.25 ms)
-int fft_group_in(int C) { return C % kFusCh == 0 ? kFusCh : 1; }
-
-}  // namespace
-
-// The row pass writes an intermediate the column pass reads straight back.  Both run on chunks of images small enough for
-// that intermediate (9.4 MB per 92 x 92 x 256 image) to stay in the 256 MB Infinity Cache.
-#ifndef EQA_FFT_CHUNK_BYTES
-#define EQA_FFT_CHUNK_BYTES (96ull << 20)
-#endif
-static int fft_chunk_images(int nimg, int rows, int TX, int C) {
+// The two-pass kernels: the row pass writes an intermediate the column pass reads straight back.  Both run on chunks of images
+// small enough for that intermediate (9.4 MB per 92 x 92 x 256 image) to stay in the 256 MB Infinity Cache.
+constexpr size_t kFftChunkBytes = 96ull << 20;
+int fft_chunk_images(int nimg, int rows, int TX, int C) {
   const size_t per_img = (size_t)rows * TX * kFftH * 2 * C * sizeof(float);
-  size_t n = EQA_FFT_CHUNK_BYTES / (per_img ? per_img : 1);
+  size_t n = kFftChunkBytes / (per_img ? per_img : 1);
   if (n < 1) n = 1;
   return (int)(n < (size_t)nimg ? n : (size_t)nimg);
 }
-
-// stats != nullptr (NB == 0 only): the pipeline's STATS form, or EQA_ERR_UNSUPPORTED where the pipeline does not apply;
-// stats_rows != nullptr: no launch, *stats_rows = the partial rows that form writes (0: it does not apply)
-template <int NB>
-static int fft_output_impl(const float* Mo, float* T2, const float* bias, int relu, float* out, int nimg, int OH, int OW, int C,
-                           hipStream_t st, int* fused, double* stats = nullptr, int64_t* stats_rows = nullptr) {
-  const int TY = (OH + kFftO - 1) / kFftO, TX = (OW + kFftO - 1) / kFftO;
-  const size_t M = (size_t)nimg * TY * TX;
-  if (stats_rows) *stats_rows = 0;
-  if ((size_t)nimg * OH > 0x7fffffffULL || M * kFftH > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
-  *fused = 0;
-  static const bool two_pass = getenv("EQA_FFT_TWO_PASS") != nullptr;
-  // persistent producer / consumer pipeline (EQA_FFT_INV_PIPE=0: one block per work item); with window-sum pieces the buffer
-  // must hold 2 NB + 6 TY segments per image (it has OH)
-  static const bool pipe_on = []() { const char* e = getenv("EQA_FFT_INV_PIPE"); return !(e && e[0] == '0'); }();
-  if (pipe_on && kInvCh == 16 && C % kInvCh == 0 && M * (C / kInvCh) <= 0x7fffffffULL && !two_pass &&
-      (size_t)kFftF * fft_pitch(M) * C * 8 <= 0xffffff00ULL && (NB == 0 || 2 * NB + (kPipeCons / 64) * TY <= OH)) {
-    constexpr int lds_bytes = kFftH * (kFftN * 2 * kInvCh + kInvCh) * (int)sizeof(float);
-    const bool lds_ok = allow_dynamic_lds((const void*)fft48_inv_pipe_kernel<NB, kInvCh>, lds_bytes);
-    static const int n_cu = []() { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    if (lds_ok) {
-      const unsigned nwork = (unsigned)(M * (C / kInvCh));
-      const unsigned blocks = nwork < (unsigned)n_cu ? nwork : (unsigned)(n_cu / kXcd * kXcd);
-      const size_t mo_total = (size_t)kFftF * fft_pitch(M) * C * 8;
-      if constexpr (NB == 0) {
-        if (stats || stats_rows) {
-          if (!allow_dynamic_lds((const void*)fft48_inv_pipe_kernel<0, kInvCh, true>, lds_bytes)) return EQA_ERR_UNSUPPORTED;
-          if (stats_rows) { *stats_rows = (int64_t)M * (kPipeCons / 64); return EQA_OK; }
-          hipLaunchKernelGGL((fft48_inv_pipe_kernel<0, kInvCh, true>), dim3(blocks), dim3(kPipeThreads), lds_bytes, st, Mo, bias, relu, out,
-                             OH, OW, C, TY, TX, fft_pitch(M), nwork, mo_total <= 0xfffffff0ULL ? (unsigned)mo_total : 0u, stats);
-          *fused = 3;
-          return hipGetLastError() == hipSuccess ? EQA_OK : EQA_ERR_LAUNCH;
-        }
-      }
-      hipLaunchKernelGGL((fft48_inv_pipe_kernel<NB, kInvCh>), dim3(blocks), dim3(kPipeThreads), lds_bytes, st, Mo, bias, relu, out, OH,
-                         OW, C, TY, TX, fft_pitch(M), nwork, mo_total <= 0xfffffff0ULL ? (unsigned)mo_total : 0u, (double*)nullptr);
-      *fused = 3;
-      return hipGetLastError() == hipSuccess ? EQA_OK : EQA_ERR_LAUNCH;
-    }
-    (void)hipGetLastError();
-  }
-  if (stats || stats_rows) return EQA_ERR_UNSUPPORTED;
-  if (C % kInvCh == 0 && M * (C / kInvCh) <= 0x7fffffffULL && !two_pass) {
-    constexpr int lds_bytes = kFftH * (kFftN * 2 * kInvCh + kInvCh) * (int)sizeof(float);
-    const bool lds_ok = allow_dynamic_lds((const void*)fft48_inv_fused_kernel<NB, kInvCh>, lds_bytes);
-    if (lds_ok) {
-      const unsigned nwork = (unsigned)(M * (C / kInvCh));
-      const size_t mo_total = (size_t)kFftF * fft_pitch(M) * C * 8;      // bytes of Mo; 0 to the kernel = beyond 32-bit offsets
-      hipLaunchKernelGGL((fft48_inv_fused_kernel<NB, kInvCh>), dim3(nwork), dim3(kFftN * kInvCh), lds_bytes, st, Mo, bias, relu, out, OH,
-                         OW, C, TY, TX, fft_pitch(M), nwork, mo_total <= 0xfffffff0ULL ? (unsigned)mo_total : 0u);
-      *fused = 1;
-      return hipGetLastError() == hipSuccess ? EQA_OK : EQA_ERR_LAUNCH;
-    }
-    (void)hipGetLastError();
-  }
-  const unsigned cb = (C + kThreads - 1) / kThreads;
-  const int chunk = fft_chunk_images(nimg, OH, TX, C);
-  for (int i0 = 0; i0 < nimg; i0 += chunk) {
-    const int n = std::min(chunk, nimg - i0);
-    hipLaunchKernelGGL((fft48_cols_inv_kernel<false, kFftO>), dim3((unsigned)((size_t)n * TY * TX * kFftH), cb), dim3(kThreads), 0, st, Mo, T2, OH, C,
-                       TY, TX, fft_pitch(M), (size_t)i0 * TY * TX);
-    hipLaunchKernelGGL((fft48_rows_inv_kernel<NB, kFftO>), dim3((unsigned)((size_t)n * OH), cb), dim3(kThreads), 0, st, T2, bias, relu, out, OH,
-                       OW, C, TX, (size_t)i0);
-  }
-  return hipGetLastError() == hipSuccess ? EQA_OK : EQA_ERR_LAUNCH;
-}
-
-extern "C" {
-#ifdef EQA_FFT_CLOCK
-int eqa_debug_fft_clock(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fft_clock), sizeof(g_fft_clock)) == hipSuccess ? 0 : -1; }
-#endif
-
-int eqa_fft48k5_group(int C, int side) {
-  if (C <= 0 || (side != 0 && side != 1)) return EQA_ERR_INVALID_ARG;
-  return side == 0 ? fft_group_in(C) : 1;
-}
-
-int eqa_fft48k5_frequencies(void) { return kFftF; }
-
-int64_t eqa_fft48k5_tiles(int n) { return n <= 4 ? 0 : (n - 4 + kFftO - 1) / kFftO; }
-
-int64_t eqa_fft48k5_tile_pitch(int64_t tiles) { return tiles <= 0 ? 0 : (int64_t)fft_pitch((size_t)tiles); }
-
-int eqa_fft48k5_filter_spectra(const float* bank, float* B, int Cout, int Cin, int correlate, void* stream) {
-  if (!bank || !B || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (((uintptr_t)B & 7) || Cin > 65535) return EQA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(fft48_filter_spectra_kernel<5>, dim3(Cin, (Cout + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, bank,
-                     B, Cout, Cin, fft_group_in(Cin), correlate ? 1.0f : -1.0f);
-  return launch_status();
-}
-
-int eqa_fft48k5_filter_spectra3m(const float* bank, float* B3, int Cout, int Cin, int correlate, void* stream) {
-  if (!bank || !B3 || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (((uintptr_t)B3 & 15) || Cin % 32 || Cout % 64 || Cin / 4 > 65535) return EQA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(fft48_filter_spectra3m_kernel<5>, dim3(Cin / 4, (Cout + kThreads - 1) / kThreads, kFftH), dim3(kThreads), 0,
-                     (hipStream_t)stream, bank, B3, Cout, Cin, correlate ? 1.0f : -1.0f);
-  return launch_status();
-}
-
-int eqa_fft48k5_input_grad(const float* Cg, float* T2, float* dx, int nimg, int H, int W, int C, void* stream) {
-  if (!Cg || !T2 || !dx || nimg < 0 || H < 5 || W < 5 || C <= 0) return EQA_ERR_INVALID_ARG;
-  if (nimg == 0) return EQA_OK;
-  const int OH = H - 4, OW = W - 4;
-  const int TY = (OH + kFftO - 1) / kFftO, TX = (OW + kFftO - 1) / kFftO;
-  const size_t M = (size_t)nimg * TY * TX;
-  if ((size_t)nimg * H > 0x7fffffffULL || M * kFftH > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned cb = (C + kThreads - 1) / kThreads;
-  // chunks of images, as in the other two-pass paths (T2 holds 48 rows per tile row here)
-  const int chunk = fft_chunk_images(nimg, TY * kFftN, TX, C);
-  for (int i0 = 0; i0 < nimg; i0 += chunk) {
-    const int n = std::min(chunk, nimg - i0);
-    hipLaunchKernelGGL((fft48_cols_inv_kernel<true, kFftO>), dim3((unsigned)((size_t)n * TY * TX * kFftH), cb), dim3(kThreads), 0, st, Cg, T2, OH,
-                       C, TY, TX, fft_pitch(M), (size_t)i0 * TY * TX);
-    hipLaunchKernelGGL(fft48_rows_inv_add_kernel<kFftO>, dim3((unsigned)((size_t)n * H), cb), dim3(kThreads), 0, st, T2,
-                       dx + (size_t)i0 * H * W * C, H, W, C, TY, TX);
-  }
-  return launch_status();
-}
-
-int64_t eqa_fft48k5_workspace_bytes(int nimg, int rows, int cols, int C) {
-  if (nimg <= 0 || rows <= 0 || cols <= 0 || C <= 0) return 0;
-  const int TX = (cols + kFftO - 1) / kFftO;  // callers pass the OUTPUT width (input width - 4) for either direction
+int64_t fft_workspace_bytes(int nimg, int rows, int cols, int C, int O) {
+  const int TX = fft_ntiles(cols, O);  // callers pass the OUTPUT width (input width - (k - 1)) for either direction
   return (int64_t)fft_chunk_images(nimg, rows, TX, C) * rows * TX * kFftH * 2 * C * (int64_t)sizeof(float);
 }
-
-static int fft_forward_impl(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C,
-                            int TY, int TX, int win, hipStream_t st, int x_grouped = 0) {
-  const size_t M = (size_t)nimg * TY * TX;
-  if ((size_t)nimg * H * TX > 0x7fffffffULL || M * kFftH > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
-  static const bool two_pass = getenv("EQA_FFT_TWO_PASS") != nullptr;  // ablation switch: the unfused passes
-  if (C % kFusCh == 0 && M * (C / kFusCh) <= 0x7fffffffULL && !two_pass) {
-    const bool lds_ok = allow_dynamic_lds((const void*)fft48_fwd_fused_kernel<kFftO>, kFusLds * 4);
-    if (lds_ok) {
-      const unsigned nwork = (unsigned)(M * (C / kFusCh));
-      const size_t xb = (size_t)nimg * H * W * C * 4, vb = (size_t)kFftF * fft_pitch(M) * 2 * C * 4;     // 0 = beyond 32-bit offsets
-      // the pipelined form: a plain channel-group-major map, every tile full-width, 32-bit offsets, enough items to keep 256 blocks busy
-      const char* pipe_env = getenv("EQA_FFT_FWD_PIPE");      // "1": opt in to the pipelined form (read per call: tests toggle it)
-      const bool pipe_off = !(pipe_env != nullptr && pipe_env[0] == '1');
-      const bool pipe_lds_ok = allow_dynamic_lds((const void*)fft48_fwd_pipe_kernel, kFusLds * 4);
-      const bool full_width = W >= kFftN && (W - kFftN) % kFftO == 0 && TX == (W - kFftN) / kFftO + 1;
-      if (!pipe_off && pipe_lds_ok && x_grouped && !in_bias && !in_relu && full_width && xb <= 0xffffe000ULL && vb <= 0xfffffff0ULL &&
-          nwork >= 2048 && (size_t)nimg * (C / kFusCh) * H <= 0x7fffffffULL) {
-        const unsigned nblk = 256;   // one persistent block per CU
-        hipLaunchKernelGGL(fft48_fwd_pipe_kernel, dim3(nblk), dim3(kFwdPipeThreads), kFusLds * sizeof(float), st, x, V, H, W, C, TY, TX,
-                           fft_pitch(M), nwork, win, (unsigned)xb, (unsigned)vb);
-        return launch_status();
-      }
-      hipLaunchKernelGGL(fft48_fwd_fused_kernel<kFftO>, dim3(nwork), dim3(kFusThreads), kFusLds * sizeof(float), st, x, V, in_bias, in_relu, H,
-                         W, C, TY, TX, fft_pitch(M), nwork, win, xb <= 0xfffffff0ULL ? (unsigned)xb : 0u,
-                         vb <= 0xfffffff0ULL ? (unsigned)vb : 0u, x_grouped);
-      return launch_status();
-    }
-    (void)hipGetLastError();
-  }
-  if (x_grouped) return EQA_ERR_UNSUPPORTED;  // only the fused kernel reads the grouped layout
-  const unsigned cb = (C + kThreads - 1) / kThreads;
-  const int chunk = fft_chunk_images(nimg, H, TX, C);
-  for (int i0 = 0; i0 < nimg; i0 += chunk) {
-    const int n = std::min(chunk, nimg - i0);
-    hipLaunchKernelGGL(fft48_rows_fwd_kernel<kFftO>, dim3((unsigned)((size_t)n * H * TX), cb), dim3(kThreads), 0, st,
-                       x + (size_t)i0 * H * W * C, T, in_bias, in_relu, H, W, C, TX, win);
-    hipLaunchKernelGGL(fft48_cols_fwd_kernel<kFftO>, dim3((unsigned)((size_t)n * TY * TX * kFftH), cb), dim3(kThreads), 0, st, T, V, H, C,
-                       TY, TX, fft_pitch(M), (size_t)i0 * TY * TX, fft_group_in(C), win);
-  }
-  return launch_status();
+// launch(i0, n): both passes for images i0 .. i0 + n - 1; `rows` intermediate rows per image
+template <class Launch>
+void fft_for_chunks(int nimg, int rows, int TX, int C, Launch launch) {
+  const int chunk = fft_chunk_images(nimg, rows, TX, C);
+  for (int i0 = 0; i0 < nimg; i0 += chunk) launch(i0, std::min(chunk, nimg - i0));
 }
 
-int eqa_fft48k5_input(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C,
-                      void* stream) {
-  if (!x || !T || !V || !fft_dims_ok(nimg, H, W, C)) return EQA_ERR_INVALID_ARG;
-  if (nimg == 0) return EQA_OK;
-  return fft_forward_impl(x, T, V, in_bias, in_relu, nimg, H, W, C, (int)eqa_fft48k5_tiles(H), (int)eqa_fft48k5_tiles(W), kFftN,
-                          (hipStream_t)stream);
-}
-
-int eqa_fft48k5_input_grouped_supported(int C) {
-  static const bool two_pass = getenv("EQA_FFT_TWO_PASS") != nullptr;
-  return C > 0 && C % kFusCh == 0 && !two_pass;
-}
-
-int eqa_fft48k5_input_grouped(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C,
-                              void* stream) {
-  if (!x || !T || !V || !fft_dims_ok(nimg, H, W, C)) return EQA_ERR_INVALID_ARG;
-  if (!eqa_fft48k5_input_grouped_supported(C)) return EQA_ERR_UNSUPPORTED;
-  if (nimg == 0) return EQA_OK;
-  return fft_forward_impl(x, T, V, in_bias, in_relu, nimg, H, W, C, (int)eqa_fft48k5_tiles(H), (int)eqa_fft48k5_tiles(W), kFftN,
-                          (hipStream_t)stream, 1);
-}
-
-int eqa_fft48k5_grad_transform(const float* dy, float* T, float* G, int nimg, int OH, int OW, int C, void* stream) {
-  if (!dy || !T || !G || nimg < 0 || OH <= 0 || OW <= 0 || C <= 0) return EQA_ERR_INVALID_ARG;
-  if (nimg == 0) return EQA_OK;
-  return fft_forward_impl(dy, T, G, nullptr, 0, nimg, OH, OW, C, (OH + kFftO - 1) / kFftO, (OW + kFftO - 1) / kFftO, kFftO,
-                          (hipStream_t)stream);
-}
-
-int eqa_fft48k5_filter_grad(const float* D, float* dbank, int Cout, int Cin, void* stream) {
-  if (!D || !dbank || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (Cin > 65535) return EQA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((fft48_filter_grad_kernel<false, 5>), dim3(Cin, (Cout + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, D,
-                     dbank, Cout, Cin, fft_group_in(Cin), fft_group_in(Cout));
-  return launch_status();
-}
-
-int eqa_fft48k5_filter_grad3m(const float* D, float* dbank, int Cout, int Cin, void* stream) {
-  if (!D || !dbank || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (Cin > 65535 || Cin % kFusCh || Cout % kFusCh) return EQA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((fft48_filter_grad_kernel<true, 5>), dim3(Cin, (Cout + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, D,
-                     dbank, Cout, Cin, kFusCh, kFusCh);
-  return launch_status();
-}
-
-int eqa_fft48k5_output(const float* Mo, float* T2, const float* bias, int relu, float* y, int nimg, int OH, int OW, int C,
-                       void* stream) {
-  if (!Mo || !T2 || !y || nimg < 0 || OH <= 0 || OW <= 0 || C <= 0) return EQA_ERR_INVALID_ARG;
-  if (nimg == 0) return EQA_OK;
-  int fused = 0;
-  const int rc = fft_output_impl<0>(Mo, T2, bias, relu, y, nimg, OH, OW, C, (hipStream_t)stream, &fused);
-  return rc != EQA_OK ? rc : launch_status();
-}
-
-int64_t eqa_fft48k5_output_stats_rows(int nimg, int OH, int OW, int C) {
-  if (nimg <= 0 || OH <= 0 || OW <= 0 || C <= 0) return 0;
-  int fused = 0;
-  int64_t rows = 0;
-  const int rc = fft_output_impl<0>(nullptr, nullptr, nullptr, 0, nullptr, nimg, OH, OW, C, nullptr, &fused, nullptr, &rows);
-  return rc == EQA_OK ? rows : 0;
-}
-
-int eqa_fft48k5_output_stats(const float* Mo, float* T2, float* y, double* partial, int nimg, int OH, int OW, int C, void* stream) {
-  if (!Mo || !T2 || !y || !partial || nimg < 0 || OH <= 0 || OW <= 0 || C <= 0) return EQA_ERR_INVALID_ARG;
-  if (nimg == 0) return EQA_OK;
-  int fused = 0;
-  const int rc = fft_output_impl<0>(Mo, T2, nullptr, 0, y, nimg, OH, OW, C, (hipStream_t)stream, &fused, partial);
-  return rc != EQA_OK ? rc : launch_status();
-}
-
-int eqa_fft48k5_output_sums(const float* Mo, float* T2, const float* bias, int relu, double* S, void* workspace, int nimg,
-                            int OH, int OW, int C, int k_next, void* stream) {
-  if (!Mo || !T2 || !S || !workspace || nimg < 0 || OH <= 0 || OW <= 0 || C <= 0 || k_next <= 0) return EQA_ERR_INVALID_ARG;
-  const int nb = k_next - 1;
-  if ((nb != 4 && nb != 2) || OH < 2 * nb + 1 || OW < 2 * nb + 1 || k_next > kMaxWinK || nimg > 65535) return EQA_ERR_UNSUPPORTED;
-  if (nimg == 0) return EQA_OK;
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace;  // (nimg, OH, TX, C, 1 + 2 nb) floats
-  int fused = 0;
-  const int rc = nb == 4 ? fft_output_impl<4>(Mo, T2, bias, relu, part, nimg, OH, OW, C, st, &fused)
-                         : fft_output_impl<2>(Mo, T2, bias, relu, part, nimg, OH, OW, C, st, &fused);
-  if (rc != EQA_OK) return rc;
-  // fused path: 2 nb border rows + one segment per tile row, each in `sub` = TX pieces; two-pass path: one per output row
-  const int sub = fused ? (OW + kFftO - 1) / kFftO : 1;
-  // interior pieces per tile row: 1 (one block per item), 5 (pipeline: one per consumer wave)
-  const int per_row = fused == 3 ? kPipeCons / 64 : fused;
-  const int nseg = fused ? 2 * nb + per_row * ((OH + kFftO - 1) / kFftO) : OH;
-  return eqa::launch_window_sums_nhwc_finalize(part, S, nimg, C, k_next, nseg * sub, st, sub);
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// Any odd kernel size 3 .. 9 (round 4): the same overlap-save scheme with 48 x 48 tiles of O = 49 - k outputs.  The forward, gradient
-// and output transforms use the fused kernels instantiated for O where C % 16 == 0 (two-pass kernels otherwise and for the input
-// gradient); no pipelined inverse and no window-sum epilogue off k = 5: the caller runs eqa_window_sums_nhwc on the map.  The reference's kernel_size is a free constructor argument (escnn_networks.py:19-44): its tutorial trains k = 9, its own test
-// k = 3.  The multiply count per output falls with k^2: 1154 x 3 real products per 40 x 40 outputs and channel pair at k = 9 against
-// 81 in the direct form (37x fewer; tiles that fit the map badly give some of it back).  The per-frequency channel contraction is
-// k-independent: eqa_fft48k5_cgemm3m / _wgrad3m / torch.bmm on buffers of eqa_fft48k5_tile_pitch rows, as for k = 5.
-// ------------------------------------------------------------------------------------------------------------------------------
-namespace {
+// The persistent pipelines (fft48_fwd_pipe_kernel, fft48_inv_pipe_kernel) are written for 44-output tiles: a plan with another
+// tile size that is asked for one answers EQA_ERR_UNSUPPORTED.
+struct FftFwdOpts {
+  int x_grouped = 0;      // the map is stored (img, channel group of 16, y, x, 16): fused kernels only
+  bool may_pipe = false;  // EQA_FFT_FWD_PIPE=1 may pick the persistent pipeline, which reads the grouped layout only -- two
+                          // options because the layout is the caller's fact and the pipeline the caller's permission
+};
+struct FftInvOpts {
+  bool may_pipe = false;          // the persistent pipeline where it applies (written for 44-output tiles)
+  double* stats = nullptr;        // NB == 0: the pipeline's STATS form, or EQA_ERR_UNSUPPORTED where the pipeline does not apply
+  int64_t* stats_rows = nullptr;  // no launch: *stats_rows = the partial rows the STATS form writes (0: it does not apply)
+  int* form = nullptr;            // out: 0 two-pass, 1 one block per item, 3 pipeline (the layout of the window-sum pieces)
+};
 
 template <int KS>
 struct FftK {
   static constexpr int O = kFftN + 1 - KS;
 
   static int forward(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C, int TY, int TX,
-                     int win, hipStream_t st) {
-    const size_t M = (size_t)nimg * TY * TX;
-    if ((size_t)nimg * H * TX > 0x7fffffffULL || M * kFftH > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
-    static const bool two_pass = getenv("EQA_FFT_TWO_PASS") != nullptr;
-    if (C % kFusCh == 0 && M * (C / kFusCh) <= 0x7fffffffULL && !two_pass &&
-        allow_dynamic_lds((const void*)fft48_fwd_fused_kernel<O>, kFusLds * 4)) {
-      // row pass, LDS, column pass in one block per (tile, 16 channels): the spectra are written once and nothing is read back
-      const unsigned nwork = (unsigned)(M * (C / kFusCh));
-      const size_t xb = (size_t)nimg * H * W * C * 4, vb = (size_t)kFftF * fft_pitch(M) * 2 * C * 4;
-      hipLaunchKernelGGL(fft48_fwd_fused_kernel<O>, dim3(nwork), dim3(kFusThreads), kFusLds * sizeof(float), st, x, V, in_bias, in_relu, H,
-                         W, C, TY, TX, fft_pitch(M), nwork, win, xb <= 0xfffffff0ULL ? (unsigned)xb : 0u,
-                         vb <= 0xfffffff0ULL ? (unsigned)vb : 0u, 0);
-      return launch_status();
+                     int win, hipStream_t st, const FftFwdOpts& opt = FftFwdOpts()) {
+    const FftTiles t(nimg, TY, TX);
+    if (!t.in_range((size_t)nimg * H * TX) || (opt.may_pipe && O != kFftO)) return EQA_ERR_UNSUPPORTED;
+    if (t.fusable(C)) {
+      if (allow_dynamic_lds((const void*)fft48_fwd_fused_kernel<O>, kFusLdsBytes)) {
+        // row pass, LDS, column pass in one block per (tile, 16 channels): the spectra are written once and nothing is read back
+        const unsigned nwork = t.nwork(C);
+        const size_t xb = (size_t)nimg * H * W * C * 4, vb = t.spectra_bytes(C);
+        if (opt.may_pipe && pipe_applies(t, xb, vb, nwork, in_bias, in_relu, nimg, H, W, C, opt)) {
+          const unsigned nblk = 256;   // one persistent block per CU
+          hipLaunchKernelGGL(fft48_fwd_pipe_kernel, dim3(nblk), dim3(kFwdPipeThreads), kFusLdsBytes, st, x, V, H, W, C, TY, TX, t.pitch,
+                             nwork, win, (unsigned)xb, (unsigned)vb);
+          return launch_status();
+        }
+        hipLaunchKernelGGL(fft48_fwd_fused_kernel<O>, dim3(nwork), dim3(kFusThreads), kFusLdsBytes, st, x, V, in_bias, in_relu, H, W, C, TY,
+                           TX, t.pitch, nwork, win, fft_desc_bytes(xb), fft_desc_bytes(vb), opt.x_grouped);
+        return launch_status();
+      }
+      (void)hipGetLastError();
     }
+    if (opt.x_grouped) return EQA_ERR_UNSUPPORTED;  // only the fused kernel reads the grouped layout
     const unsigned cb = (C + kThreads - 1) / kThreads;
-    const int chunk = fft_chunk_images(nimg, H, TX, C);
-    for (int i0 = 0; i0 < nimg; i0 += chunk) {
-      const int n = std::min(chunk, nimg - i0);
+    fft_for_chunks(nimg, H, TX, C, [&](int i0, int n) {
       hipLaunchKernelGGL(fft48_rows_fwd_kernel<O>, dim3((unsigned)((size_t)n * H * TX), cb), dim3(kThreads), 0, st,
                          x + (size_t)i0 * H * W * C, T, in_bias, in_relu, H, W, C, TX, win);
       hipLaunchKernelGGL(fft48_cols_fwd_kernel<O>, dim3((unsigned)((size_t)n * TY * TX * kFftH), cb), dim3(kThreads), 0, st, T, V, H, C,
-                         TY, TX, fft_pitch(M), (size_t)i0 * TY * TX, fft_group_in(C), win);
-    }
+                         TY, TX, t.pitch, (size_t)i0 * TY * TX, fft_group_in(C), win);
+    });
     return launch_status();
   }
 
-  static int output(const float* Mo, float* T2, const float* bias, int relu, float* y, int nimg, int OH, int OW, int C, hipStream_t st) {
-    const int TY = (OH + O - 1) / O, TX = (OW + O - 1) / O;
-    const size_t M = (size_t)nimg * TY * TX;
-    if ((size_t)nimg * OH > 0x7fffffffULL || M * kFftH > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
-    static const bool two_pass = getenv("EQA_FFT_TWO_PASS") != nullptr;
-    constexpr int lds_bytes = kFftH * (kFftN * 2 * kInvCh + kInvCh) * (int)sizeof(float);
-    if (C % kInvCh == 0 && M * (C / kInvCh) <= 0x7fffffffULL && !two_pass &&
-        allow_dynamic_lds((const void*)fft48_inv_fused_kernel<0, kInvCh, O>, lds_bytes)) {
-      const unsigned nwork = (unsigned)(M * (C / kInvCh));
-      const size_t mo_total = (size_t)kFftF * fft_pitch(M) * C * 8;
-      hipLaunchKernelGGL((fft48_inv_fused_kernel<0, kInvCh, O>), dim3(nwork), dim3(kFftN * kInvCh), lds_bytes, st, Mo, bias, relu, y, OH, OW, C,
-                         TY, TX, fft_pitch(M), nwork, mo_total <= 0xfffffff0ULL ? (unsigned)mo_total : 0u);
-      return launch_status();
+  // The pipelined forward: opted in per call (tests toggle EQA_FFT_FWD_PIPE), a plain channel-group-major map, every tile
+  // full-width, 32-bit offsets, enough items to keep 256 blocks busy.
+  static bool pipe_applies(const FftTiles& t, size_t xb, size_t vb, unsigned nwork, const float* in_bias, int in_relu, int nimg, int H,
+                           int W, int C, const FftFwdOpts& opt) {
+    const char* env = getenv("EQA_FFT_FWD_PIPE");
+    if (!(env != nullptr && env[0] == '1') || !allow_dynamic_lds((const void*)fft48_fwd_pipe_kernel, kFusLdsBytes)) return false;
+    const bool full_width = W >= kFftN && (W - kFftN) % kFftO == 0 && t.TX == (W - kFftN) / kFftO + 1;
+    return opt.x_grouped && !in_bias && !in_relu && full_width && xb <= 0xffffe000ULL && vb <= 0xfffffff0ULL && nwork >= 2048 &&
+           (size_t)nimg * (C / kFusCh) * H <= 0x7fffffffULL;
+  }
+
+  // NB = k_next - 1 > 0: the window-sum pieces of the next layer instead of the map (44-output tiles only)
+  template <int NB>
+  static int output(const float* Mo, float* T2, const float* bias, int relu, float* out, int nimg, int OH, int OW, int C, hipStream_t st,
+                    const FftInvOpts& opt = FftInvOpts()) {
+    const FftTiles t(nimg, fft_ntiles(OH, O), fft_ntiles(OW, O));
+    const int TY = t.TY, TX = t.TX;
+    const bool want_stats = opt.stats || opt.stats_rows;
+    int form_ = 0;
+    int& form = opt.form ? *opt.form : form_;
+    form = 0;
+    if (opt.stats_rows) *opt.stats_rows = 0;
+    if (!t.in_range((size_t)nimg * OH) || (opt.may_pipe && O != kFftO)) return EQA_ERR_UNSUPPORTED;
+    const unsigned nwork = t.fusable(C) ? t.nwork(C) : 0u;
+    const size_t mo_bytes = t.spectra_bytes(C);
+    // persistent producer / consumer pipeline; with window-sum pieces the buffer must hold 2 NB + 5 TY segments per image (it has OH)
+    if (opt.may_pipe && fft_inv_pipe_on() && t.fusable(C) && mo_bytes <= 0xffffff00ULL && (NB == 0 || 2 * NB + (kPipeCons / 64) * TY <= OH)) {
+      if (allow_dynamic_lds((const void*)fft48_inv_pipe_kernel<NB, kFusCh>, kFusLdsBytes)) {
+        static const int n_cu = []() { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+        const unsigned blocks = nwork < (unsigned)n_cu ? nwork : (unsigned)(n_cu / kXcd * kXcd);
+        if constexpr (NB == 0) {
+          if (want_stats) {
+            if (!allow_dynamic_lds((const void*)fft48_inv_pipe_kernel<0, kFusCh, true>, kFusLdsBytes)) return EQA_ERR_UNSUPPORTED;
+            if (opt.stats_rows) { *opt.stats_rows = (int64_t)t.M * (kPipeCons / 64); return EQA_OK; }
+            hipLaunchKernelGGL((fft48_inv_pipe_kernel<0, kFusCh, true>), dim3(blocks), dim3(kPipeThreads), kFusLdsBytes, st, Mo, bias, relu,
+                               out, OH, OW, C, TY, TX, t.pitch, nwork, fft_desc_bytes(mo_bytes), opt.stats);
+            form = 3;
+            return launch_status();
+          }
+        }
+        hipLaunchKernelGGL((fft48_inv_pipe_kernel<NB, kFusCh>), dim3(blocks), dim3(kPipeThreads), kFusLdsBytes, st, Mo, bias, relu, out, OH,
+                           OW, C, TY, TX, t.pitch, nwork, fft_desc_bytes(mo_bytes), (double*)nullptr);
+        form = 3;
+        return launch_status();
+      }
+      (void)hipGetLastError();
+    }
+    if (want_stats) return EQA_ERR_UNSUPPORTED;
+    if (t.fusable(C)) {
+      if (allow_dynamic_lds((const void*)fft48_inv_fused_kernel<NB, kFusCh, O>, kFusLdsBytes)) {
+        hipLaunchKernelGGL((fft48_inv_fused_kernel<NB, kFusCh, O>), dim3(nwork), dim3(kFusThreads), kFusLdsBytes, st, Mo, bias, relu, out, OH,
+                           OW, C, TY, TX, t.pitch, nwork, fft_desc_bytes(mo_bytes));
+        form = 1;
+        return launch_status();
+      }
+      (void)hipGetLastError();
     }
     const unsigned cb = (C + kThreads - 1) / kThreads;
-    const int chunk = fft_chunk_images(nimg, OH, TX, C);
-    for (int i0 = 0; i0 < nimg; i0 += chunk) {
-      const int n = std::min(chunk, nimg - i0);
+    fft_for_chunks(nimg, OH, TX, C, [&](int i0, int n) {
       hipLaunchKernelGGL((fft48_cols_inv_kernel<false, O>), dim3((unsigned)((size_t)n * TY * TX * kFftH), cb), dim3(kThreads), 0, st, Mo, T2,
-                         OH, C, TY, TX, fft_pitch(M), (size_t)i0 * TY * TX);
-      hipLaunchKernelGGL((fft48_rows_inv_kernel<0, O>), dim3((unsigned)((size_t)n * OH), cb), dim3(kThreads), 0, st, T2, bias, relu, y, OH,
+                         OH, C, TY, TX, t.pitch, (size_t)i0 * TY * TX);
+      hipLaunchKernelGGL((fft48_rows_inv_kernel<NB, O>), dim3((unsigned)((size_t)n * OH), cb), dim3(kThreads), 0, st, T2, bias, relu, out, OH,
                          OW, C, TX, (size_t)i0);
-    }
+    });
     return launch_status();
   }
 
   static int input_grad(const float* Cg, float* T2, float* dx, int nimg, int H, int W, int C, hipStream_t st) {
     const int OH = H - (KS - 1), OW = W - (KS - 1);
-    const int TY = (OH + O - 1) / O, TX = (OW + O - 1) / O;
-    const size_t M = (size_t)nimg * TY * TX;
-    if ((size_t)nimg * H > 0x7fffffffULL || M * kFftH > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
+    const FftTiles t(nimg, fft_ntiles(OH, O), fft_ntiles(OW, O));
+    const int TY = t.TY, TX = t.TX;
+    if (!t.in_range((size_t)nimg * H)) return EQA_ERR_UNSUPPORTED;
     const unsigned cb = (C + kThreads - 1) / kThreads;
-    const int chunk = fft_chunk_images(nimg, TY * kFftN, TX, C);
-    for (int i0 = 0; i0 < nimg; i0 += chunk) {
-      const int n = std::min(chunk, nimg - i0);
+    // chunks of images, as in the other two-pass paths (T2 holds 48 rows per tile row here)
+    fft_for_chunks(nimg, TY * kFftN, TX, C, [&](int i0, int n) {
       hipLaunchKernelGGL((fft48_cols_inv_kernel<true, O>), dim3((unsigned)((size_t)n * TY * TX * kFftH), cb), dim3(kThreads), 0, st, Cg, T2,
-                         OH, C, TY, TX, fft_pitch(M), (size_t)i0 * TY * TX);
+                         OH, C, TY, TX, t.pitch, (size_t)i0 * TY * TX);
       hipLaunchKernelGGL(fft48_rows_inv_add_kernel<O>, dim3((unsigned)((size_t)n * H), cb), dim3(kThreads), 0, st, T2,
                          dx + (size_t)i0 * H * W * C, H, W, C, TY, TX);
-    }
-    return launch_status();
-  }
-
-  static int spectra(const float* bank, float* B, int Cout, int Cin, float sgn, hipStream_t st) {
-    hipLaunchKernelGGL(fft48_filter_spectra_kernel<KS>, dim3(Cin, (Cout + kThreads - 1) / kThreads), dim3(kThreads), 0, st, bank, B, Cout,
-                       Cin, fft_group_in(Cin), sgn);
-    return launch_status();
-  }
-  static int spectra3m(const float* bank, float* B3, int Cout, int Cin, float sgn, hipStream_t st) {
-    hipLaunchKernelGGL(fft48_filter_spectra3m_kernel<KS>, dim3(Cin / 4, (Cout + kThreads - 1) / kThreads, kFftH), dim3(kThreads), 0, st, bank,
-                       B3, Cout, Cin, sgn);
-    return launch_status();
-  }
-  static int filter_grad(const float* D, float* dbank, int Cout, int Cin, bool packed, hipStream_t st) {
-    // fewer than ~2 blocks per CU in the one-thread-per-filter form: one thread per filter ROW instead
-    if ((size_t)Cin * ((Cout + kThreads - 1) / kThreads) < 512) {
-      const dim3 grid(Cin, (Cout + kThreads - 1) / kThreads, KS);
-      if (packed)
-        hipLaunchKernelGGL((fft48_filter_grad_rows_kernel<true, KS>), grid, dim3(kThreads), 0, st, D, dbank, Cout, Cin, kFusCh, kFusCh);
-      else
-        hipLaunchKernelGGL((fft48_filter_grad_rows_kernel<false, KS>), grid, dim3(kThreads), 0, st, D, dbank, Cout, Cin, fft_group_in(Cin),
-                           fft_group_in(Cout));
-      return launch_status();
-    }
-    if (packed)
-      hipLaunchKernelGGL((fft48_filter_grad_kernel<true, KS>), dim3(Cin, (Cout + kThreads - 1) / kThreads), dim3(kThreads), 0, st, D, dbank,
-                         Cout, Cin, kFusCh, kFusCh);
-    else
-      hipLaunchKernelGGL((fft48_filter_grad_kernel<false, KS>), dim3(Cin, (Cout + kThreads - 1) / kThreads), dim3(kThreads), 0, st, D, dbank,
-                         Cout, Cin, fft_group_in(Cin), fft_group_in(Cout));
+    });
     return launch_status();
   }
 };
 
-inline bool fft_ksize_ok(int k) { return k == 3 || k == 5 || k == 7 || k == 9; }
-inline int fft_tiles_k(int n, int k) { return n < k ? 0 : (n - (k - 1) + (kFftN + 1 - k) - 1) / (kFftN + 1 - k); }
-
-#define EQA_FFT_K(ksize, expr)                 \
-  switch (ksize) {                             \
-    case 3: { using K_ = FftK<3>; return expr; } \
-    case 5: { using K_ = FftK<5>; return expr; } \
-    case 7: { using K_ = FftK<7>; return expr; } \
-    case 9: { using K_ = FftK<9>; return expr; } \
-    default: return EQA_ERR_UNSUPPORTED;       \
-  }
+// argument checks shared by the two families of entry points (k = 5 for eqa_fft48k5_*)
+bool fft_map_args_ok(const void* a, const void* b, const void* c, int nimg, int rows, int cols, int C) {
+  return a && b && c && nimg >= 0 && rows > 0 && cols > 0 && C > 0;
+}
+bool fft_input_args_ok(const void* a, const void* b, const void* c, int nimg, int H, int W, int C, int ksize) {
+  return a && b && c && nimg >= 0 && C > 0 && fft_ksize_ok(ksize) && H >= ksize && W >= ksize;
+}
 
 }  // namespace
 
 extern "C" {
+#ifdef EQA_FFT_CLOCK
+int eqa_debug_fft_clock(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fft_clock), sizeof(g_fft_clock)) == hipSuccess ? 0 : -1; }
+#endif
+
+int eqa_fft48k5_frequencies(void) { return kFftF; }
+
+int64_t eqa_fft48k5_tiles(int n) { return fft_tiles_k(n, 5); }
+
+int64_t eqa_fft48k5_tile_pitch(int64_t tiles) { return tiles <= 0 ? 0 : (int64_t)fft_pitch((size_t)tiles); }
+
+int64_t eqa_fft48k5_workspace_bytes(int nimg, int rows, int cols, int C) {
+  if (nimg <= 0 || rows <= 0 || cols <= 0 || C <= 0) return 0;
+  return fft_workspace_bytes(nimg, rows, cols, C, kFftO);
+}
+
+int eqa_fft48k5_input(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C,
+                      void* stream) {
+  if (!fft_input_args_ok(x, T, V, nimg, H, W, C, 5)) return EQA_ERR_INVALID_ARG;
+  if (nimg == 0) return EQA_OK;
+  return FftK<5>::forward(x, T, V, in_bias, in_relu, nimg, H, W, C, fft_tiles_k(H, 5), fft_tiles_k(W, 5), kFftN, (hipStream_t)stream);
+}
+
+int eqa_fft48k5_input_grouped_supported(int C) { return C > 0 && C % kFusCh == 0 && !fft_two_pass(); }
+
+int eqa_fft48k5_input_grouped(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C,
+                              void* stream) {
+  if (!fft_input_args_ok(x, T, V, nimg, H, W, C, 5)) return EQA_ERR_INVALID_ARG;
+  if (!eqa_fft48k5_input_grouped_supported(C)) return EQA_ERR_UNSUPPORTED;
+  if (nimg == 0) return EQA_OK;
+  FftFwdOpts opt;
+  opt.x_grouped = 1;
+  opt.may_pipe = true;
+  return FftK<5>::forward(x, T, V, in_bias, in_relu, nimg, H, W, C, fft_tiles_k(H, 5), fft_tiles_k(W, 5), kFftN, (hipStream_t)stream, opt);
+}
+
+int eqa_fft48k5_grad_transform(const float* dy, float* T, float* G, int nimg, int OH, int OW, int C, void* stream) {
+  if (!fft_map_args_ok(dy, T, G, nimg, OH, OW, C)) return EQA_ERR_INVALID_ARG;
+  if (nimg == 0) return EQA_OK;
+  return FftK<5>::forward(dy, T, G, nullptr, 0, nimg, OH, OW, C, fft_ntiles(OH, kFftO), fft_ntiles(OW, kFftO), kFftO, (hipStream_t)stream);
+}
+
+int eqa_fft48k5_input_grad(const float* Cg, float* T2, float* dx, int nimg, int H, int W, int C, void* stream) {
+  if (!fft_input_args_ok(Cg, T2, dx, nimg, H, W, C, 5)) return EQA_ERR_INVALID_ARG;
+  if (nimg == 0) return EQA_OK;
+  return FftK<5>::input_grad(Cg, T2, dx, nimg, H, W, C, (hipStream_t)stream);
+}
+
+int eqa_fft48k5_output(const float* Mo, float* T2, const float* bias, int relu, float* y, int nimg, int OH, int OW, int C,
+                       void* stream) {
+  if (!fft_map_args_ok(Mo, T2, y, nimg, OH, OW, C)) return EQA_ERR_INVALID_ARG;
+  if (nimg == 0) return EQA_OK;
+  FftInvOpts opt;
+  opt.may_pipe = true;
+  return FftK<5>::output<0>(Mo, T2, bias, relu, y, nimg, OH, OW, C, (hipStream_t)stream, opt);
+}
+
+int64_t eqa_fft48k5_output_stats_rows(int nimg, int OH, int OW, int C) {
+  if (nimg <= 0 || OH <= 0 || OW <= 0 || C <= 0) return 0;
+  int64_t rows = 0;
+  FftInvOpts opt;
+  opt.may_pipe = true;
+  opt.stats_rows = &rows;
+  return FftK<5>::output<0>(nullptr, nullptr, nullptr, 0, nullptr, nimg, OH, OW, C, nullptr, opt) == EQA_OK ? rows : 0;
+}
+
+int eqa_fft48k5_output_stats(const float* Mo, float* T2, float* y, double* partial, int nimg, int OH, int OW, int C, void* stream) {
+  if (!fft_map_args_ok(Mo, T2, y, nimg, OH, OW, C) || !partial) return EQA_ERR_INVALID_ARG;
+  if (nimg == 0) return EQA_OK;
+  FftInvOpts opt;
+  opt.may_pipe = true;
+  opt.stats = partial;
+  return FftK<5>::output<0>(Mo, T2, nullptr, 0, y, nimg, OH, OW, C, (hipStream_t)stream, opt);
+}
+
+int eqa_fft48k5_output_sums(const float* Mo, float* T2, const float* bias, int relu, double* S, void* workspace, int nimg,
+                            int OH, int OW, int C, int k_next, void* stream) {
+  if (!fft_map_args_ok(Mo, T2, S, nimg, OH, OW, C) || !workspace || k_next <= 0) return EQA_ERR_INVALID_ARG;
+  const int nb = k_next - 1;
+  if ((nb != 4 && nb != 2) || OH < 2 * nb + 1 || OW < 2 * nb + 1 || k_next > kMaxWinK || nimg > 65535) return EQA_ERR_UNSUPPORTED;
+  if (nimg == 0) return EQA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)workspace;  // (nimg, OH, TX, C, 1 + 2 nb) floats
+  int form = 0;
+  FftInvOpts opt;
+  opt.may_pipe = true;
+  opt.form = &form;
+  const int rc = nb == 4 ? FftK<5>::output<4>(Mo, T2, bias, relu, part, nimg, OH, OW, C, st, opt)
+                         : FftK<5>::output<2>(Mo, T2, bias, relu, part, nimg, OH, OW, C, st, opt);
+  if (rc != EQA_OK) return rc;
+  // fused forms: 2 nb border rows + one segment per tile row, each in `sub` = TX pieces; two-pass: one per output row
+  const int sub = form ? fft_ntiles(OW, kFftO) : 1;
+  // interior pieces per tile row: 1 (one block per item), 5 (pipeline: one per consumer wave)
+  const int per_row = form == 3 ? kPipeCons / 64 : form;
+  const int nseg = form ? 2 * nb + per_row * fft_ntiles(OH, kFftO) : OH;
+  return eqa::launch_window_sums_nhwc_finalize(part, S, nimg, C, k_next, nseg * sub, st, sub);
+}
 
 int eqa_fft48_supported(int ksize) { return fft_ksize_ok(ksize) ? 1 : 0; }
 
@@ -1660,55 +1247,35 @@ int64_t eqa_fft48_tiles(int n, int ksize) { return fft_ksize_ok(ksize) ? fft_til
 
 int64_t eqa_fft48_workspace_bytes(int nimg, int rows, int cols, int C, int ksize) {
   if (nimg <= 0 || rows <= 0 || cols <= 0 || C <= 0 || !fft_ksize_ok(ksize)) return 0;
-  const int O = kFftN + 1 - ksize;
-  const int TX = (cols + O - 1) / O;     // callers pass the OUTPUT width (input width - (k - 1)) for either direction
-  return (int64_t)fft_chunk_images(nimg, rows, TX, C) * rows * TX * kFftH * 2 * C * (int64_t)sizeof(float);
-}
-
-int eqa_fft48_filter_spectra(const float* bank, float* B, int Cout, int Cin, int ksize, int correlate, void* stream) {
-  if (!bank || !B || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (((uintptr_t)B & 7) || Cin > 65535) return EQA_ERR_UNSUPPORTED;
-  EQA_FFT_K(ksize, K_::spectra(bank, B, Cout, Cin, correlate ? 1.0f : -1.0f, (hipStream_t)stream));
-}
-
-int eqa_fft48_filter_spectra3m(const float* bank, float* B3, int Cout, int Cin, int ksize, int correlate, void* stream) {
-  if (!bank || !B3 || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (((uintptr_t)B3 & 15) || Cin % 32 || Cout % 64 || Cin / 4 > 65535) return EQA_ERR_UNSUPPORTED;
-  EQA_FFT_K(ksize, K_::spectra3m(bank, B3, Cout, Cin, correlate ? 1.0f : -1.0f, (hipStream_t)stream));
+  return fft_workspace_bytes(nimg, rows, cols, C, kFftN + 1 - ksize);
 }
 
 int eqa_fft48_input(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C, int ksize,
                     void* stream) {
-  if (!x || !T || !V || nimg < 0 || C <= 0 || !fft_ksize_ok(ksize) || H < ksize || W < ksize) return EQA_ERR_INVALID_ARG;
+  if (!fft_input_args_ok(x, T, V, nimg, H, W, C, ksize)) return EQA_ERR_INVALID_ARG;
   if (nimg == 0) return EQA_OK;
-  EQA_FFT_K(ksize, K_::forward(x, T, V, in_bias, in_relu, nimg, H, W, C, fft_tiles_k(H, ksize), fft_tiles_k(W, ksize), kFftN,
-                               (hipStream_t)stream));
+  EQA_FFT_K(ksize, FftK, K_::forward(x, T, V, in_bias, in_relu, nimg, H, W, C, fft_tiles_k(H, ksize), fft_tiles_k(W, ksize), kFftN,
+                                     (hipStream_t)stream));
 }
 
 int eqa_fft48_grad_transform(const float* dy, float* T, float* G, int nimg, int OH, int OW, int C, int ksize, void* stream) {
-  if (!dy || !T || !G || nimg < 0 || OH <= 0 || OW <= 0 || C <= 0 || !fft_ksize_ok(ksize)) return EQA_ERR_INVALID_ARG;
+  if (!fft_map_args_ok(dy, T, G, nimg, OH, OW, C) || !fft_ksize_ok(ksize)) return EQA_ERR_INVALID_ARG;
   if (nimg == 0) return EQA_OK;
-  EQA_FFT_K(ksize, K_::forward(dy, T, G, nullptr, 0, nimg, OH, OW, C, (OH + K_::O - 1) / K_::O, (OW + K_::O - 1) / K_::O, K_::O,
-                               (hipStream_t)stream));
+  EQA_FFT_K(ksize, FftK, K_::forward(dy, T, G, nullptr, 0, nimg, OH, OW, C, fft_ntiles(OH, K_::O), fft_ntiles(OW, K_::O), K_::O,
+                                     (hipStream_t)stream));
 }
 
 int eqa_fft48_output(const float* Mo, float* T2, const float* bias, int relu, float* y, int nimg, int OH, int OW, int C, int ksize,
                      void* stream) {
-  if (!Mo || !T2 || !y || nimg < 0 || OH <= 0 || OW <= 0 || C <= 0 || !fft_ksize_ok(ksize)) return EQA_ERR_INVALID_ARG;
+  if (!fft_map_args_ok(Mo, T2, y, nimg, OH, OW, C) || !fft_ksize_ok(ksize)) return EQA_ERR_INVALID_ARG;
   if (nimg == 0) return EQA_OK;
-  EQA_FFT_K(ksize, K_::output(Mo, T2, bias, relu, y, nimg, OH, OW, C, (hipStream_t)stream));
+  EQA_FFT_K(ksize, FftK, K_::template output<0>(Mo, T2, bias, relu, y, nimg, OH, OW, C, (hipStream_t)stream));
 }
 
 int eqa_fft48_input_grad(const float* Cg, float* T2, float* dx, int nimg, int H, int W, int C, int ksize, void* stream) {
-  if (!Cg || !T2 || !dx || nimg < 0 || C <= 0 || !fft_ksize_ok(ksize) || H < ksize || W < ksize) return EQA_ERR_INVALID_ARG;
+  if (!fft_input_args_ok(Cg, T2, dx, nimg, H, W, C, ksize)) return EQA_ERR_INVALID_ARG;
   if (nimg == 0) return EQA_OK;
-  EQA_FFT_K(ksize, K_::input_grad(Cg, T2, dx, nimg, H, W, C, (hipStream_t)stream));
-}
-
-int eqa_fft48_filter_grad(const float* D, float* dbank, int Cout, int Cin, int ksize, int packed, void* stream) {
-  if (!D || !dbank || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
-  if (Cin > 65535 || (packed && (Cin % kFusCh || Cout % kFusCh))) return EQA_ERR_UNSUPPORTED;
-  EQA_FFT_K(ksize, K_::filter_grad(D, dbank, Cout, Cin, packed != 0, (hipStream_t)stream));
+  EQA_FFT_K(ksize, FftK, K_::input_grad(Cg, T2, dx, nimg, H, W, C, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -128,9 +128,7 @@ __global__ __launch_bounds__(kThreads) void winograd_k5_input_kernel(const float
   // (bijective form for nwork % 8 != 0).  Input pixels are shared by overlapping tiles; with neighbouring strips on one
   // XCD the overlap is served by that XCD's L2 instead of being re-fetched from HBM (measured, m = 2, tiles dealt
   // round-robin: 3.6 GB fetched per 0.55 GB of input; with this order 0.55 GB).
-  const size_t bid = blockIdx.x;
-  const size_t q8 = nwork / kXcd, r8 = nwork % kXcd, xcd = bid % kXcd;
-  const size_t work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / kXcd;  // (img*TY + ty)*nstrip + s
+  const size_t work = xcd_work_order<size_t>(blockIdx.x, nwork);  // (img*TY + ty)*nstrip + s
   const int s = (int)(work % nstrip);
   const size_t r = work / nstrip;  // img*TY + ty
   const int ty = (int)(r % TY);

@@ -62,6 +62,9 @@ SIGNATURES = {
     "eqa_vn_convpos_fwd": (_int, [_vp] * 7 + [_int, _int, _int, _vp]),
     "eqa_vn_convpos_bwd_reduce": (_int, [_vp] * 10 + [_int, _int, _int, _vp]),
     "eqa_vn_convpos_bwd_apply": (_int, [_vp] * 12 + [_int, _int, _int, _vp]),
+    "eqa_vn_convpos_max_fwd": (_int, [_vp] * 9 + [_int, _int, _int, _vp]),
+    "eqa_vn_convpos_max_bwd_reduce": (_int, [_vp] * 11 + [_int, _int, _int, _vp]),
+    "eqa_vn_convpos_max_bwd_apply": (_int, [_vp] * 13 + [_int, _int, _int, _vp]),
     "eqa_vn_tail_blocks": (_int, [_int]),
     "eqa_vn_tail_partial_floats": (_int, [_int]),
     "eqa_vn_tail_pass": (_int, [_int] + [_vp] * 8 + [_int, _int, _vp]),

@@ -9,6 +9,14 @@
 //   eqa_vn_convpos_fwd         q = W_f f; q <- q / n * (n * scale + shift); gate by d = W_d f; mean over k  -> (B, 21, 3, N)
 //   eqa_vn_convpos_bwd_reduce  per-channel sums of g and g * nhat (g = dL/d BN output): d beta, d gamma, batch-norm terms
 //   eqa_vn_convpos_bwd_apply   d W_f, d W_d (126 partial sums per block)
+// pooling = "max" (VNMaxPool, vector_neuron_layers.py:327-364) instead of the mean: per (cloud, channel, point) the edge with the
+// largest <h_c, (W_p h)_c> is gathered, h = the block's 21 output vectors of that edge.  Statistics, finalize: the passes above.
+//   eqa_vn_convpos_max_fwd         the gathered vectors (B, 21, 3, N) and the winner's position in the point's neighbour list
+//                                  sel (B, 21, N) uint8: first maximum in list order, as torch.max
+//   eqa_vn_convpos_max_bwd_reduce  the mean pass's sums with the output gradient given whole to edge sel, nothing to the others
+//   eqa_vn_convpos_max_bwd_apply   d W_f, d W_d likewise.  The edges that lost still move with the batch statistics (the -m1 - nhat m2
+//                                  terms of the batch-norm backward), so this pass walks all k edges, with a zero output gradient
+//                                  off the winner.  W_p only feeds the argmax: no gradient.
 // No gradient w.r.t. the point coordinates (the cloud is data).  C ABI: include/eqa_hip.h.
 #include "vn_common.hpp"
 
@@ -29,6 +37,12 @@ __device__ __forceinline__ VnEdge vn_edge(const V3& ctr, const float4& nb4) {
 __device__ __forceinline__ V3 vn_mix(const float* __restrict__ w, const VnEdge& e) {  // w[0..2]: one output channel
   return v3(w[0] * e.f0.x + w[1] * e.f1.x + w[2] * e.f2.x, w[0] * e.f0.y + w[1] * e.f1.y + w[2] * e.f2.y,
             w[0] * e.f0.z + w[1] * e.f1.z + w[2] * e.f2.z);
+}
+
+// One output vector of the block's forward: h_c = gate(bn(W_f[c] e), W_d[c] e)
+__device__ __forceinline__ V3 vn_convpos_h(const float* __restrict__ wf, const float* __restrict__ wd, float scale, float shift,
+                                           const VnEdge& e) {
+  return vn_relu_sel(vn_bn(vn_mix(wf, e), scale, shift), vn_mix(wd, e));
 }
 
 // block-wide sum of NV per-thread values -> out[0..NV) (deterministic: shuffles, then a fixed-order sum over the waves)
@@ -171,7 +185,7 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_fwd_kernel(const float*
     V3 a = v3(0.f, 0.f, 0.f);
 #pragma unroll
     for (int t = 0; t < EMAX; ++t) {
-      const V3 q = vn_relu_sel(vn_bn(vn_mix(Wf + 3 * c, e[t]), sc, sh), vn_mix(Wd + 3 * c, e[t]));
+      const V3 q = vn_convpos_h(Wf + 3 * c, Wd + 3 * c, sc, sh, e[t]);
       a.x += m[t] * q.x; a.y += m[t] * q.y; a.z += m[t] * q.z;
     }
     acc[c] = a;
@@ -196,23 +210,112 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_fwd_kernel(const float*
   }
 }
 
+// The quad's best (score, list position) of one channel, to all four lanes: the larger score, on equal scores the lower position
+// (the first maximum of the list, torch.max's; the rule of the fused eval kernel, pointcloud.hip).  A lane without a live edge
+// holds (-inf, 255) and never wins.
+template <int CTRL>
+__device__ __forceinline__ void vn_quad_better(float& s, int& p) {
+  const float os = vn_dpp_f<CTRL>(s);
+  const int op = vn_dpp_i<CTRL>(p);
+  const bool take = os > s || (os == s && op < p);
+  s = take ? os : s;
+  p = take ? op : p;
+}
+
+// VNMaxPool over the point's k edges.  Edge-outer (one edge's 21 vectors h are all needed for its 21 scores), the channel loops
+// unrolled.  Only the running best score and its position are kept per channel (42 registers beside the 63 of h); once the quad
+// has agreed on the winners, lane `sub` evaluates the winning edge again for the channels c = sub, sub + 4, ... it stores: six
+// (edge, channel) evaluations per lane after 21 x edges, instead of 63 more live registers and three selects per score.
+// The edge loop is rolled (its trip count is ceil(k / 4) for the whole wave), so one kernel serves every k <= 32.
+// hipcc -Rpass-analysis=kernel-resource-usage, gfx950: 126 VGPRs, 106 SGPRs, scratch 0 -> 4 waves per SIMD (512 registers per lane).
+__global__ __launch_bounds__(kVnThreads) void vn_convpos_max_fwd_kernel(const float* __restrict__ x, const int32_t* __restrict__ idx,
+                                                                       const float* __restrict__ Wf, const float* __restrict__ Wd,
+                                                                       const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                       const float* __restrict__ Wp, float* __restrict__ pooled,
+                                                                       uint8_t* __restrict__ sel, int N, int k) {
+  VN_PASS_PROLOGUE
+  float best[kVnC];
+  int pos[kVnC];
+#pragma unroll
+  for (int c = 0; c < kVnC; ++c) {
+    best[c] = -INFINITY;
+    pos[c] = 255;
+  }
+#pragma unroll 1
+  for (int t = 0; t < edges; ++t) {      // lane 0 of every quad owns `edges` positions: wave-uniform trip count
+    asm volatile("" ::: "memory");       // keep the weights in the scalar cache, not hoisted into VGPRs (see pointcloud.hip)
+    const bool live = active && t < cnt;
+    const VnEdge e = vn_edge(ctr, pts[nbr[t < cnt ? t : 0]]);
+    V3 h[kVnC];
+#pragma unroll
+    for (int c = 0; c < kVnC; ++c) h[c] = vn_convpos_h(Wf + 3 * c, Wd + 3 * c, scale[c], shift[c], e);
+    const int p = sub * edges + t;
+#pragma unroll
+    for (int c = 0; c < kVnC; ++c) {
+      if (c % 3 == 0) asm volatile("" ::: "memory");
+      V3 d = v3(0.f, 0.f, 0.f);
+#pragma unroll
+      for (int a = 0; a < kVnC; ++a) {
+        const float w = Wp[c * kVnC + a];
+        d.x += w * h[a].x; d.y += w * h[a].y; d.z += w * h[a].z;
+      }
+      const float s = dot3(h[c], d);
+      const bool take = live && s > best[c];   // strict: the first maximal edge (lowest position) wins, as torch.max does
+      best[c] = take ? s : best[c];
+      pos[c] = take ? p : pos[c];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kVnC; ++c) {
+    vn_quad_better<0xB1>(best[c], pos[c]);  // [1,0,3,2]
+    vn_quad_better<0x4E>(best[c], pos[c]);  // [2,3,0,1]
+  }
+  const int32_t* row = idx + ((size_t)b * N + (active ? n : N - 1)) * k;
+  float* o = pooled + (size_t)b * kVnC * 3 * N + (active ? n : N - 1);  // (B, 21, 3, N)
+  uint8_t* os = sel + (size_t)b * kVnC * N + (active ? n : N - 1);      // (B, 21, N)
+#pragma unroll
+  for (int c0 = 0; c0 < kVnC; c0 += kVnSplit) {
+    int p = pos[c0];
+#pragma unroll
+    for (int u = 1; u < kVnSplit; ++u)
+      if (c0 + u < kVnC) p = sub == u ? pos[c0 + u] : p;
+    p = min(p, k - 1);   // (255 is left only where no score compared greater than -inf: NaN input)
+    const int c = min(c0 + sub, kVnC - 1);
+    const V3 hv = vn_convpos_h(Wf + 3 * c, Wd + 3 * c, scale[c], shift[c], vn_edge(ctr, pts[row[p]]));
+    if (active && c0 + sub < kVnC) {
+      o[(size_t)(3 * c) * N] = hv.x;
+      o[(size_t)(3 * c + 1) * N] = hv.y;
+      o[(size_t)(3 * c + 2) * N] = hv.z;
+      os[(size_t)c * N] = (uint8_t)p;
+    }
+  }
+}
+
 // One (edge, channel) of the block: mix the edge features, then the shared layer gradient (vn_common.hpp)
 __device__ __forceinline__ VnGrad vn_edge_grad(const float* __restrict__ wf, const float* __restrict__ wd, const VnEdge& e,
                                                float scale, float shift, const V3& g_out) {
   return vn_gate_grad(vn_mix(wf, e), vn_mix(wd, e), scale, shift, g_out);
 }
 
-template <int EMAX>
+// The two backward passes serve both poolings (MAXPOOL: compile time).  mean: every edge of the point gets the channel's output
+// gradient / k.  max: the edge at list position sel gets it whole, the others none.  `sel` is a kernel argument of the max
+// instantiation only (the trailing pack), so the mean instantiation's argument block is what it was.
+__device__ __forceinline__ const uint8_t* vn_sel_arg() { return nullptr; }
+__device__ __forceinline__ const uint8_t* vn_sel_arg(const uint8_t* sel) { return sel; }
+
+template <int EMAX, bool MAXPOOL = false, class... Sel>
 __global__ __launch_bounds__(kVnThreads) void vn_convpos_bwd_reduce_kernel(const float* __restrict__ x, const int32_t* __restrict__ idx,
                                                                           const float* __restrict__ Wf, const float* __restrict__ Wd,
                                                                           const float* __restrict__ scale, const float* __restrict__ shift,
                                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                           const float* __restrict__ gpool, float* __restrict__ partial,
-                                                                          int N, int k) {
+                                                                          int N, int k, Sel... sel) {
   __shared__ float s_red[(kVnThreads / 64) * 2 * kVnC];   // per wave, all channels: ONE barrier after the channel loop, not two per channel
   VN_PASS_PROLOGUE
-  const float inv_k = active ? 1.0f / (float)k : 0.0f;  // idle threads contribute nothing
+  // an edge's share of the channel's output gradient: 1 / k, or all of it for the winner; idle threads contribute nothing
+  const float share = active ? (MAXPOOL ? 1.0f : 1.0f / (float)k) : 0.0f;
   const float* gp = gpool + (size_t)b * kVnC * 3 * N + (active ? n : N - 1);
+  const uint8_t* sp = MAXPOOL ? vn_sel_arg(sel...) + (size_t)b * kVnC * N + (active ? n : N - 1) : nullptr;
   int nb[EMAX];
 #pragma unroll
   for (int t = 0; t < EMAX; ++t) nb[t] = nbr[t < cnt ? t : 0];
@@ -220,9 +323,18 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_bwd_reduce_kernel(const
   // channel by channel (the output gradient of a channel is the same for all k edges of the point): two accumulators live
 #pragma unroll 1
   for (int c = 0; c < kVnC; ++c) {
-    const V3 g_out = v3(gp[(size_t)(3 * c) * N] * inv_k, gp[(size_t)(3 * c + 1) * N] * inv_k, gp[(size_t)(3 * c + 2) * N] * inv_k);
+    const V3 g_out = v3(gp[(size_t)(3 * c) * N] * share, gp[(size_t)(3 * c + 1) * N] * share, gp[(size_t)(3 * c + 2) * N] * share);
     const float sc = scale[c], sh = shift[c], mu = mean[c], rs = rstd[c];
     float acc[2] = {0.f, 0.f};
+    if constexpr (MAXPOOL) {
+      // the sums are over g_nbn, which is zero off the winner: one edge of the point, in the lane that owns its position
+      const int t = (int)sp[(size_t)c * N] - sub * edges;
+      if (t >= 0 && t < cnt) {
+        const VnGrad r = vn_edge_grad(Wf + 3 * c, Wd + 3 * c, vn_edge(ctr, pts[nbr[t]]), sc, sh, g_out);
+        acc[0] += r.g_nbn;
+        acc[1] += r.g_nbn * (r.nr - mu) * rs;
+      }
+    } else {
 #pragma unroll
     for (int t = 0; t < EMAX; ++t) {
       if (t < cnt) {   // (k = 20, EMAX = 5: always true)
@@ -230,6 +342,7 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_bwd_reduce_kernel(const
         acc[0] += r.g_nbn;
         acc[1] += r.g_nbn * (r.nr - mu) * rs;
       }
+    }
     }
     vn_wave_part<2>(acc, s_red, 2 * kVnC, 2 * c);
   }
@@ -239,32 +352,36 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_bwd_reduce_kernel(const
 // dW_f[c][i] = sum <g_q, f_i>, dW_d[c][i] = sum <g_d, f_i>;  g_q = dL/dq through the direction u = q/n and through the norm:
 //   g_n = gamma rstd (g_nbn - m1 - nhat m2)   (m1 = sum g_nbn / M, m2 = sum g_nbn nhat / M; both 0 with running statistics)
 //   g_q = (g_u - u <g_u, q> / |q|) / n + g_n q / |q|,   g_u = g_qn * nbn
-template <int EMAX>
+// max pooling: g_nbn is zero off the winner but m1 and m2 are not, so with batch statistics every edge has a g_n: all k edges
+// are walked, the losers with a zero output gradient.
+template <int EMAX, bool MAXPOOL = false, class... Sel>
 __global__ __launch_bounds__(kVnThreads) void vn_convpos_bwd_apply_kernel(const float* __restrict__ x, const int32_t* __restrict__ idx,
                                                                          const float* __restrict__ Wf, const float* __restrict__ Wd,
                                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                          const float* __restrict__ m1, const float* __restrict__ m2,
                                                                          const float* __restrict__ gpool, float* __restrict__ partial,
-                                                                         int N, int k) {
+                                                                         int N, int k, Sel... sel) {
   __shared__ float s_red[(kVnThreads / 64) * 6 * kVnC];
   VN_PASS_PROLOGUE
-  const float inv_k = active ? 1.0f / (float)k : 0.0f;
+  const float share = active ? (MAXPOOL ? 1.0f : 1.0f / (float)k) : 0.0f;
   const float* gp = gpool + (size_t)b * kVnC * 3 * N + (active ? n : N - 1);
+  const uint8_t* sp = MAXPOOL ? vn_sel_arg(sel...) + (size_t)b * kVnC * N + (active ? n : N - 1) : nullptr;
   int nb[EMAX];
 #pragma unroll
   for (int t = 0; t < EMAX; ++t) nb[t] = nbr[t < cnt ? t : 0];
   float* out = partial + ((size_t)b * gridDim.x + blockIdx.x) * (6 * kVnC);  // [c][W_f 0..2, W_d 0..2]
 #pragma unroll 1
   for (int c = 0; c < kVnC; ++c) {
-    const V3 g_out = v3(gp[(size_t)(3 * c) * N] * inv_k, gp[(size_t)(3 * c + 1) * N] * inv_k, gp[(size_t)(3 * c + 2) * N] * inv_k);
+    const V3 g_out = v3(gp[(size_t)(3 * c) * N] * share, gp[(size_t)(3 * c + 1) * N] * share, gp[(size_t)(3 * c + 2) * N] * share);
     const float sc = scale[c], sh = shift[c], mu = mean[c], rs = rstd[c], mm1 = m1[c], mm2 = m2[c];
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int won = MAXPOOL ? (int)sp[(size_t)c * N] - sub * edges : 0;   // the winner's slot in this lane's share, if it is here
 #pragma unroll
     for (int t = 0; t < EMAX; ++t) {
       if (t < cnt) {
         const VnEdge e = vn_edge(ctr, pts[nb[t]]);
-        const VnGrad r = vn_edge_grad(Wf + 3 * c, Wd + 3 * c, e, sc, sh, g_out);
+        const VnGrad r = vn_edge_grad(Wf + 3 * c, Wd + 3 * c, e, sc, sh, MAXPOOL && t != won ? v3(0.f, 0.f, 0.f) : g_out);
         const V3 g_q = vn_norm_input_grad(r, sc, mu, rs, mm1, mm2, active);
         acc[0] += dot3(g_q, e.f0);
         acc[1] += dot3(g_q, e.f1);
@@ -358,6 +475,50 @@ int eqa_vn_convpos_bwd_apply(const float* x, const int32_t* idx, const float* Wf
   if (rc != 1) return rc;
   if (!Wf || !Wd || !scale || !shift || !mean || !rstd || !m1 || !m2 || !gpool || !partial) return EQA_ERR_INVALID_ARG;
   VN_LAUNCH_E(vn_convpos_bwd_apply_kernel, x, idx, Wf, Wd, scale, shift, mean, rstd, m1, m2, gpool, partial, N, k);
+  return launch_status();
+}
+
+// ---- pooling = "max"
+#define VN_LAUNCH_E_MAX(kernel, ...)                                                                                     \
+  do {                                                                                                                   \
+    if (k <= 20)                                                                                                         \
+      hipLaunchKernelGGL((kernel<5, true, const uint8_t*>), dim3(eqa_vn_blocks(N), B), dim3(kVnThreads), lds,            \
+                         (hipStream_t)stream, __VA_ARGS__);                                                              \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((kernel<8, true, const uint8_t*>), dim3(eqa_vn_blocks(N), B), dim3(kVnThreads), lds,            \
+                         (hipStream_t)stream, __VA_ARGS__);                                                              \
+  } while (0)
+
+int eqa_vn_convpos_max_fwd(const float* x, const int32_t* idx, const float* Wf, const float* Wd, const float* scale,
+                           const float* shift, const float* Wp, float* pooled, uint8_t* sel, int B, int N, int k, void* stream) {
+  size_t lds;
+  const int rc = vn_check(x, idx, B, N, k, lds, false);
+  if (rc != 1) return rc;
+  if (!Wf || !Wd || !scale || !shift || !Wp || !pooled || !sel) return EQA_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(vn_convpos_max_fwd_kernel, dim3(eqa_vn_blocks(N), B), dim3(kVnThreads), lds, (hipStream_t)stream, x, idx, Wf, Wd,
+                     scale, shift, Wp, pooled, sel, N, k);
+  return launch_status();
+}
+
+int eqa_vn_convpos_max_bwd_reduce(const float* x, const int32_t* idx, const float* Wf, const float* Wd, const float* scale,
+                                  const float* shift, const float* mean, const float* rstd, const float* gpool,
+                                  const uint8_t* sel, float* partial, int B, int N, int k, void* stream) {
+  size_t lds;
+  const int rc = vn_check(x, idx, B, N, k, lds, false);
+  if (rc != 1) return rc;
+  if (!Wf || !Wd || !scale || !shift || !mean || !rstd || !gpool || !sel || !partial) return EQA_ERR_INVALID_ARG;
+  VN_LAUNCH_E_MAX(vn_convpos_bwd_reduce_kernel, x, idx, Wf, Wd, scale, shift, mean, rstd, gpool, partial, N, k, sel);
+  return launch_status();
+}
+
+int eqa_vn_convpos_max_bwd_apply(const float* x, const int32_t* idx, const float* Wf, const float* Wd, const float* scale,
+                                 const float* shift, const float* mean, const float* rstd, const float* m1, const float* m2,
+                                 const float* gpool, const uint8_t* sel, float* partial, int B, int N, int k, void* stream) {
+  size_t lds;
+  const int rc = vn_check(x, idx, B, N, k, lds, false);
+  if (rc != 1) return rc;
+  if (!Wf || !Wd || !scale || !shift || !mean || !rstd || !m1 || !m2 || !gpool || !sel || !partial) return EQA_ERR_INVALID_ARG;
+  VN_LAUNCH_E_MAX(vn_convpos_bwd_apply_kernel, x, idx, Wf, Wd, scale, shift, mean, rstd, m1, m2, gpool, partial, N, k, sel);
   return launch_status();
 }
 

@@ -42,6 +42,91 @@ def get_graph_feature_cross(x: torch.Tensor, k: int = 20, idx: Optional[torch.Te
     return torch.cat((nbr - ctr, ctr, cross), dim=3).permute(0, 3, 4, 1, 2).contiguous()
 
 
+def _convpos_graph_and_stats(x, Wf_, gamma, beta, bn, k):
+    """What both poolings of the fused first block start from: the kNN graph and the VN batch-norm's scale | shift | mean | rstd
+    (32 floats each) of n = |W_f f| + EPS, from the statistics of all B*N*k edges in training mode (running statistics updated like
+    nn.BatchNorm2d) or from the running statistics.  Returns (idx, stat, batch_stats, M)."""
+    from equiadapt_amd import _lib, ops
+
+    lib = _lib.load()
+    B, _, N = x.shape
+    C = Wf_.shape[0]
+    st = ops._stream()
+    nblk = B * lib.eqa_vn_blocks(N)
+    dev = x.device
+    idx = torch.empty((B, N, k), dtype=torch.int32, device=dev)
+    _lib.check(lib.eqa_vn_knn(x.data_ptr(), idx.data_ptr(), B, N, k, st), "eqa_vn_knn")
+    M = B * N * k
+    batch_stats = bool(bn.training or bn.running_mean is None)
+    stat = torch.empty(128, dtype=torch.float32, device=dev)          # scale | shift | mean | rstd, 32 floats each
+    if batch_stats and (bn.momentum is not None or not bn.track_running_stats):
+        part = torch.empty((nblk, C, 2), dtype=torch.float32, device=dev)
+        _lib.check(lib.eqa_vn_convpos_stats(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), part.data_ptr(), B, N, k, st),
+                   "eqa_vn_convpos_stats")
+        track = bn.track_running_stats and bn.running_mean is not None
+        _lib.check(lib.eqa_vn_bn_finalize(part.data_ptr(), nblk, 2 * C, C, M, gamma.detach().data_ptr(), beta.detach().data_ptr(),
+                                          bn.running_mean.data_ptr() if track else None,
+                                          bn.running_var.data_ptr() if track else None,
+                                          bn.num_batches_tracked.data_ptr() if track else None,
+                                          float(bn.momentum or 0.0), float(bn.eps), stat.data_ptr(), st), "eqa_vn_bn_finalize")
+        if track:
+            mark_written(bn.running_mean, bn.running_var, bn.num_batches_tracked)
+    else:
+        if batch_stats:                                                # cumulative moving average (momentum=None): host glue
+            part = torch.empty((nblk, C, 2), dtype=torch.float32, device=dev)
+            _lib.check(lib.eqa_vn_convpos_stats(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), part.data_ptr(), B, N, k, st),
+                       "eqa_vn_convpos_stats")
+            sums = part.sum(0, dtype=torch.float64)
+            mean = sums[:, 0] / M
+            var = (sums[:, 1] / M - mean * mean).clamp_min(0.0)
+            update_running_stats(bn, mean, var * (M / max(M - 1, 1)))
+            mean, var = mean.float(), var.float()
+        else:
+            mean, var = bn.running_mean, bn.running_var
+        rstd = torch.rsqrt(var + bn.eps)
+        sc = gamma.detach() * rstd
+        stat[0:C], stat[32:32 + C], stat[64:64 + C], stat[96:96 + C] = sc, beta.detach() - mean * sc, mean, rstd
+    return idx, stat, batch_stats, M
+
+
+def _convpos_backward(x, idx, Wf, Wd, stat, gpool, k, M, batch_stats, sel=None):
+    """d W_f, d W_d, d gamma, d beta of the fused first block from the gradient of its pooled output.  sel None: mean over the
+    neighbours (eqa_vn_convpos_bwd_*); sel (B, 21, N) uint8: the max pooling's winners (eqa_vn_convpos_max_bwd_*)."""
+    from equiadapt_amd import _lib, ops
+
+    lib = _lib.load()
+    B, _, N = x.shape
+    C = Wf.shape[0]
+    scale, shift, mean, rstd = stat[0:C], stat[32:32 + C], stat[64:64 + C], stat[96:96 + C]
+    gpool = gpool.contiguous()
+    st = ops._stream()
+    nblk = B * lib.eqa_vn_blocks(N)
+    dev = x.device
+    if sel is None:
+        reduce_fn, apply_fn, names, extra = lib.eqa_vn_convpos_bwd_reduce, lib.eqa_vn_convpos_bwd_apply, "eqa_vn_convpos_bwd", ()
+    else:
+        reduce_fn, apply_fn, names, extra = (lib.eqa_vn_convpos_max_bwd_reduce, lib.eqa_vn_convpos_max_bwd_apply,
+                                             "eqa_vn_convpos_max_bwd", (sel.data_ptr(),))
+    with torch.cuda.device(dev):
+        part = torch.empty((nblk, C, 2), dtype=torch.float32, device=dev)
+        _lib.check(reduce_fn(x.data_ptr(), idx.data_ptr(), Wf.data_ptr(), Wd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                             mean.data_ptr(), rstd.data_ptr(), gpool.data_ptr(), *extra, part.data_ptr(), B, N, k, st),
+                   names + "_reduce")
+        grads = torch.empty(64, dtype=torch.float32, device=dev)            # d beta[32] | d gamma[32]
+        red = torch.empty(64, dtype=torch.float32, device=dev)              # m1[32] | m2[32]
+        _lib.check(lib.eqa_vn_bn_bwd_finalize(part.data_ptr(), nblk, 2 * C, C, M, grads.data_ptr(), red.data_ptr(), st),
+                   "eqa_vn_bn_bwd_finalize")
+        dbeta, dgamma = grads[:C], grads[32:32 + C]
+        if not batch_stats:
+            red.zero_()
+        wpart = torch.empty((nblk, C, 6), dtype=torch.float32, device=dev)
+        _lib.check(apply_fn(x.data_ptr(), idx.data_ptr(), Wf.data_ptr(), Wd.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                            mean.data_ptr(), rstd.data_ptr(), red.data_ptr(), red[32:].data_ptr(), gpool.data_ptr(), *extra,
+                            wpart.data_ptr(), B, N, k, st), names + "_apply")
+        dW = wpart.sum(0, dtype=torch.float64).float()
+    return dW[:, :3].contiguous(), dW[:, 3:].contiguous(), dgamma, dbeta
+
+
 class ConvPosMeanPool(torch.autograd.Function):
     """mean over the k neighbours of VNLinearLeakyReLU(3 -> 21, slope 0)(edge features), with autograd w.r.t. the layer's
     parameters, on the recompute-everything kernels of csrc/vnsmall_train.hip (eqa_vn_*): (B, 3, N) -> (B, 21, 3, N).
@@ -57,82 +142,54 @@ class ConvPosMeanPool(torch.autograd.Function):
         x = x.contiguous()
         Wf_, Wd_ = Wf.detach().contiguous(), Wd.detach().contiguous()
         C = Wf_.shape[0]
-        st = ops._stream()
-        nblk = B * lib.eqa_vn_blocks(N)
-        dev = x.device
-        with torch.cuda.device(dev):
-            idx = torch.empty((B, N, k), dtype=torch.int32, device=dev)
-            _lib.check(lib.eqa_vn_knn(x.data_ptr(), idx.data_ptr(), B, N, k, st), "eqa_vn_knn")
-            M = B * N * k
-            batch_stats = bool(bn.training or bn.running_mean is None)
-            stat = torch.empty(128, dtype=torch.float32, device=dev)          # scale | shift | mean | rstd, 32 floats each
-            if batch_stats and (bn.momentum is not None or not bn.track_running_stats):
-                part = torch.empty((nblk, C, 2), dtype=torch.float32, device=dev)
-                _lib.check(lib.eqa_vn_convpos_stats(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), part.data_ptr(), B, N, k, st),
-                           "eqa_vn_convpos_stats")
-                track = bn.track_running_stats and bn.running_mean is not None
-                _lib.check(lib.eqa_vn_bn_finalize(part.data_ptr(), nblk, 2 * C, C, M, gamma.detach().data_ptr(), beta.detach().data_ptr(),
-                                                  bn.running_mean.data_ptr() if track else None,
-                                                  bn.running_var.data_ptr() if track else None,
-                                                  bn.num_batches_tracked.data_ptr() if track else None,
-                                                  float(bn.momentum or 0.0), float(bn.eps), stat.data_ptr(), st), "eqa_vn_bn_finalize")
-                if track:
-                    mark_written(bn.running_mean, bn.running_var, bn.num_batches_tracked)
-            else:
-                if batch_stats:                                                # cumulative moving average (momentum=None): host glue
-                    part = torch.empty((nblk, C, 2), dtype=torch.float32, device=dev)
-                    _lib.check(lib.eqa_vn_convpos_stats(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), part.data_ptr(), B, N, k, st),
-                               "eqa_vn_convpos_stats")
-                    sums = part.sum(0, dtype=torch.float64)
-                    mean = sums[:, 0] / M
-                    var = (sums[:, 1] / M - mean * mean).clamp_min(0.0)
-                    update_running_stats(bn, mean, var * (M / max(M - 1, 1)))
-                    mean, var = mean.float(), var.float()
-                else:
-                    mean, var = bn.running_mean, bn.running_var
-                rstd = torch.rsqrt(var + bn.eps)
-                sc = gamma.detach() * rstd
-                stat[0:C], stat[32:32 + C], stat[64:64 + C], stat[96:96 + C] = sc, beta.detach() - mean * sc, mean, rstd
-            scale, shift, mean, rstd = stat[0:C], stat[32:32 + C], stat[64:64 + C], stat[96:96 + C]
-            pooled = torch.empty((B, C, 3, N), dtype=torch.float32, device=dev)
-            _lib.check(lib.eqa_vn_convpos_fwd(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), Wd_.data_ptr(), scale.data_ptr(),
-                                              shift.data_ptr(), pooled.data_ptr(), B, N, k, st), "eqa_vn_convpos_fwd")
+        with torch.cuda.device(x.device):
+            idx, stat, batch_stats, M = _convpos_graph_and_stats(x, Wf_, gamma, beta, bn, k)
+            pooled = torch.empty((B, C, 3, N), dtype=torch.float32, device=x.device)
+            _lib.check(lib.eqa_vn_convpos_fwd(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), Wd_.data_ptr(), stat[0:C].data_ptr(),
+                                              stat[32:32 + C].data_ptr(), pooled.data_ptr(), B, N, k, ops._stream()),
+                       "eqa_vn_convpos_fwd")
         ctx.save_for_backward(x, idx, Wf_, Wd_, stat)
         ctx.batch_stats, ctx.M, ctx.k = batch_stats, M, k
         return pooled
 
     @staticmethod
     def backward(ctx, gpool):
+        x, idx, Wf, Wd, stat = ctx.saved_tensors
+        dWf, dWd, dgamma, dbeta = _convpos_backward(x, idx, Wf, Wd, stat, gpool, ctx.k, ctx.M, ctx.batch_stats)
+        return None, dWf, dWd, dgamma, dbeta, None, None
+
+
+class ConvPosMaxPool(torch.autograd.Function):
+    """VNMaxPool(21) over the k neighbours of the same layer, on eqa_vn_convpos_max_*: per (cloud, channel, point) the edge with
+    the largest <h_c, (W_p h)_c> is gathered, and its position in the point's neighbour list kept (sel, uint8) for the backward,
+    which hands that edge the whole output gradient.  Graph and statistics as ConvPosMeanPool.  W_p = pool.map_to_dir.weight
+    only feeds the argmax: its gradient is None, as in autograd of the op-by-op path."""
+
+    @staticmethod
+    def forward(ctx, x, Wf, Wd, gamma, beta, Wp, bn, k):
         from equiadapt_amd import _lib, ops
 
         lib = _lib.load()
-        x, idx, Wf, Wd, stat = ctx.saved_tensors
         B, _, N = x.shape
-        C, k = Wf.shape[0], ctx.k
-        scale, shift, mean, rstd = stat[0:C], stat[32:32 + C], stat[64:64 + C], stat[96:96 + C]
-        gpool = gpool.contiguous()
-        st = ops._stream()
-        nblk = B * lib.eqa_vn_blocks(N)
-        dev = x.device
-        with torch.cuda.device(dev):
-            part = torch.empty((nblk, C, 2), dtype=torch.float32, device=dev)
-            _lib.check(lib.eqa_vn_convpos_bwd_reduce(x.data_ptr(), idx.data_ptr(), Wf.data_ptr(), Wd.data_ptr(), scale.data_ptr(),
-                                                     shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gpool.data_ptr(),
-                                                     part.data_ptr(), B, N, k, st), "eqa_vn_convpos_bwd_reduce")
-            grads = torch.empty(64, dtype=torch.float32, device=dev)            # d beta[32] | d gamma[32]
-            red = torch.empty(64, dtype=torch.float32, device=dev)              # m1[32] | m2[32]
-            _lib.check(lib.eqa_vn_bn_bwd_finalize(part.data_ptr(), nblk, 2 * C, C, ctx.M, grads.data_ptr(), red.data_ptr(), st),
-                       "eqa_vn_bn_bwd_finalize")
-            dbeta, dgamma = grads[:C], grads[32:32 + C]
-            if not ctx.batch_stats:
-                red.zero_()
-            wpart = torch.empty((nblk, C, 6), dtype=torch.float32, device=dev)
-            _lib.check(lib.eqa_vn_convpos_bwd_apply(x.data_ptr(), idx.data_ptr(), Wf.data_ptr(), Wd.data_ptr(), scale.data_ptr(),
-                                                    shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), red.data_ptr(),
-                                                    red[32:].data_ptr(), gpool.data_ptr(), wpart.data_ptr(), B, N, k, st),
-                       "eqa_vn_convpos_bwd_apply")
-            dW = wpart.sum(0, dtype=torch.float64).float()
-        return None, dW[:, :3].contiguous(), dW[:, 3:].contiguous(), dgamma, dbeta, None, None
+        x = x.contiguous()
+        Wf_, Wd_, Wp_ = Wf.detach().contiguous(), Wd.detach().contiguous(), Wp.detach().contiguous()
+        C = Wf_.shape[0]
+        with torch.cuda.device(x.device):
+            idx, stat, batch_stats, M = _convpos_graph_and_stats(x, Wf_, gamma, beta, bn, k)
+            pooled = torch.empty((B, C, 3, N), dtype=torch.float32, device=x.device)
+            sel = torch.empty((B, C, N), dtype=torch.uint8, device=x.device)
+            _lib.check(lib.eqa_vn_convpos_max_fwd(x.data_ptr(), idx.data_ptr(), Wf_.data_ptr(), Wd_.data_ptr(), stat[0:C].data_ptr(),
+                                                  stat[32:32 + C].data_ptr(), Wp_.data_ptr(), pooled.data_ptr(), sel.data_ptr(),
+                                                  B, N, k, ops._stream()), "eqa_vn_convpos_max_fwd")
+        ctx.save_for_backward(x, idx, sel, Wf_, Wd_, stat)
+        ctx.batch_stats, ctx.M, ctx.k = batch_stats, M, k
+        return pooled
+
+    @staticmethod
+    def backward(ctx, gpool):
+        x, idx, sel, Wf, Wd, stat = ctx.saved_tensors
+        dWf, dWd, dgamma, dbeta = _convpos_backward(x, idx, Wf, Wd, stat, gpool, ctx.k, ctx.M, ctx.batch_stats, sel)
+        return None, dWf, dWd, dgamma, dbeta, None, None, None
 
 
 class TailMean(torch.autograd.Function):
@@ -270,13 +327,18 @@ class VNSmall(nn.Module):
             from equiadapt_amd import ops
 
             return ops.vnsmall_forward(point_cloud, self.packed_parameters(), self.n_knn, self.pooling)
-        if (point_cloud.is_cuda and torch.is_grad_enabled() and not point_cloud.requires_grad and self.pooling == "mean"
+        if (point_cloud.is_cuda and torch.is_grad_enabled() and not point_cloud.requires_grad
+                and (self.pooling == "mean" or (self.pooling == "max" and type(self.pool) is VNMaxPool))
                 and 1 <= self.n_knn <= 32 and self.n_knn <= point_cloud.shape[-1] <= 4096 and point_cloud.dtype == torch.float32
                 and os.environ.get("EQA_TRAIN_FAST", "1") != "0"):
             # training: the (B, 21, 3, N, k) edge tensors of the first block are never materialised (csrc/vnsmall_train.hip)
             cp = self.conv_pos
-            out = ConvPosMeanPool.apply(point_cloud, cp.map_to_feat.weight, cp.map_to_dir.weight, cp.batchnorm.bn2d.weight,
-                                        cp.batchnorm.bn2d.bias, cp.batchnorm.bn2d, self.n_knn)
+            if self.pooling == "mean":
+                out = ConvPosMeanPool.apply(point_cloud, cp.map_to_feat.weight, cp.map_to_dir.weight, cp.batchnorm.bn2d.weight,
+                                            cp.batchnorm.bn2d.bias, cp.batchnorm.bn2d, self.n_knn)
+            else:
+                out = ConvPosMaxPool.apply(point_cloud, cp.map_to_feat.weight, cp.map_to_dir.weight, cp.batchnorm.bn2d.weight,
+                                           cp.batchnorm.bn2d.bias, self.pool.map_to_dir.weight, cp.batchnorm.bn2d, self.n_knn)
         else:
             feat = get_graph_feature_cross(point_cloud.unsqueeze(1), k=self.n_knn)
             out = self.pool(self.conv_pos(feat))

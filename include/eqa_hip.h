@@ -721,6 +721,26 @@ int eqa_vn_convpos_bwd_apply(const float* x, const int32_t* idx, const float* Wf
                              const float* gpool, float* partial, int B, int N, int k, void* stream);
 
 /*
+ * The same block with pooling = "max": VNMaxPool(21) instead of the mean over the neighbours (vector_neuron_layers.py:327-364
+ * VNMaxPool; equivariant_networks.py:128-140, the first block with self.pool = VNMaxPool).  Per (cloud, channel, point) the edge
+ * with the largest <h_c, (W_p h)_c> is gathered, h:(21, 3) = the block's output on that edge, Wp:(21,21) = pool.map_to_dir.weight.
+ * The statistics are over all B*N*k edges whichever edge wins: eqa_vn_convpos_stats and the finalize kernels serve both poolings.
+ *   eqa_vn_convpos_max_fwd         pooled:(B, 21, 3, N); sel:(B, 21, N) uint8 = the winner's position in the point's idx row
+ *                                  (not the neighbour id); the first maximum in list order, as torch.max
+ *   eqa_vn_convpos_max_bwd_reduce  as eqa_vn_convpos_bwd_reduce, the output gradient going whole (no 1/k) to edge sel, none to the others
+ *   eqa_vn_convpos_max_bwd_apply   as eqa_vn_convpos_bwd_apply, likewise; m1, m2 still over M = B*N*k.  No gradient for Wp.
+ * Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_vn_convpos_max_fwd(const float* x, const int32_t* idx, const float* Wf, const float* Wd, const float* scale,
+                           const float* shift, const float* Wp, float* pooled, uint8_t* sel, int B, int N, int k, void* stream);
+int eqa_vn_convpos_max_bwd_reduce(const float* x, const int32_t* idx, const float* Wf, const float* Wd, const float* scale,
+                                  const float* shift, const float* mean, const float* rstd, const float* gpool,
+                                  const uint8_t* sel, float* partial, int B, int N, int k, void* stream);
+int eqa_vn_convpos_max_bwd_apply(const float* x, const int32_t* idx, const float* Wf, const float* Wd, const float* scale,
+                                 const float* shift, const float* mean, const float* rstd, const float* m1, const float* m2,
+                                 const float* gpool, const uint8_t* sel, float* partial, int B, int N, int k, void* stream);
+
+/*
  * Training passes of VNSmall's tail on the pooled features of the first block: conv1 = VNLinearLeakyReLU(21 -> 21, slope 0) ->
  * bn1 = VNBatchNorm(21) -> conv2 = VNLinearLeakyReLU(21 -> 4, slope 0) -> dropout -> mean over the points
  * (equivariant_networks.py:141-150; vector_neuron_layers.py:251-273, :303-324), the three batch-norms in training mode, forward

@@ -37,6 +37,20 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+// The patch fetch of the matrix-core forms: one channels-last pixel (12 contiguous bytes at byte offset `off` of the images) in ONE
+// vector-memory instruction, global_load_dwordx3 (a load the compiler counts itself: profiles/r13).  Three buffer dword loads at
+// offsets 0 / 4 / 8 stood here: hipcc 7.2 does not merge them, and its __builtin_amdgcn_raw_buffer_load_b96 compiles to a single
+// buffer_load_dword (channel 0 alone arrives).  A plain load has no range check to answer "no pixel" with zeros, so a lane without one
+// (`ok` false: outside the image, or nothing to fetch) reads pixel 0 -- one address for all such lanes -- and lf_pixel_or_zero
+// discards it when the pixel is staged.
+struct alignas(4) LfPixel { float c[3]; };
+__device__ __forceinline__ void lf_fetch_pixel(float (&p)[3], const float* __restrict__ x, unsigned off, bool ok) {
+  const LfPixel v = *reinterpret_cast<const LfPixel*>(reinterpret_cast<const char*>(x) + (ok ? off : 0u));
+#pragma unroll
+  for (int c = 0; c < 3; ++c) p[c] = v.c[c];
+}
+__device__ __forceinline__ float lf_pixel_or_zero(float v, bool ok) { return ok ? v : 0.0f; }
+
 #ifdef EQA_LF_CLOCK
 // Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of five waves ([8 k .. 8 k + 7], k = slot:
 // waves 8, 1, 0, 6, 11), and HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD) -- tools/kbench_lift_fft.py.
@@ -231,19 +245,18 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
   };
 
   // PIECES: input rows in groups of four (group g = patch rows 4 g .. 4 g + 3, 13 groups per item, ring slot g % 2): thread t < 208 of
-  // the column waves owns pixel (row t / 52, x t % 52) of a group -- three dword loads one sub-phase ahead, three 8-byte LDS stores
+  // the column waves owns pixel (row t / 52, x t % 52) of a group -- fetched one sub-phase ahead, three 8-byte LDS stores
   // (one per piece plane: c0 c1 c2 0).  `which`: the register set (the last sub-phase of an item fetches two groups of the next).
   float preg[COLS && PIECES ? 2 : 1][3];
+  bool preg_ok[2] = {false, false};    // the set holds a pixel of the image
   auto prefetch_grp = [&](const LfItem& it, int g, int which, bool live) {
     if constexpr (COLS && PIECES) {
       int tq = tid;
       asm volatile("" : "+v"(tq));
       const int pr = tq / 52, px = tq - pr * 52;
       const int gy = it.gy0 + 4 * g + pr, gx = it.gx0 + px;
-      const bool ok = live && tq < 208 && gy < H0 && gx < W0;
-      const unsigned off = ok ? (unsigned)((((it.img * H0 + gy) * (size_t)W0 + gx) * 3) * 4) : 0xfffffff0u;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) preg[which][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off, c * 4, 0));
+      preg_ok[which] = live && tq < 208 && gy < H0 && gx < W0;
+      lf_fetch_pixel(preg[which], x, (unsigned)((((it.img * H0 + gy) * (size_t)W0 + gx) * 3) * 4), preg_ok[which]);
     }
   };
   auto stage_grp = [&](int g, int which) {
@@ -252,7 +265,7 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
         const int pr = tid / 52, px = tid - pr * 52;
         __bf16 pc[3][3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) lf_split3(preg[which][c], pc[0][c], pc[1][c], pc[2][c]);
+        for (int c = 0; c < 3; ++c) lf_split3(lf_pixel_or_zero(preg[which][c], preg_ok[which]), pc[0][c], pc[1][c], pc[2][c]);
         char* dst = reinterpret_cast<char*>(lds) + patch_b + ((4 * g + pr) & 7) * kLpRowB + px * 8;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
@@ -264,9 +277,10 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
   };
 
   // FORM 2: a staging unit = patch rows [row0, row0 + nrows) of an item (16 rows in front of its first sub-phase, 12 afterwards), by
-  // the 384 threads of the CONVOLUTION waves: thread t owns pixels t, t + 384, t + 768 of the unit -- three dword loads each a
+  // the 384 threads of the CONVOLUTION waves: thread t owns pixels t, t + 384, t + 768 of the unit -- fetched a
   // sub-phase ahead; behind the sub-phase's second barrier the scaled values are split and written, 8 bytes per plane.
   float preh[(!COLS && H2) ? kLhPre : 1][3];
+  unsigned preh_ok = 0;                // bit i: preh[i] holds a pixel of the image
   float x_scale = 1.0f, out_scale = 1.0f;
   if constexpr (H2) {
     float mx = 0.0f;
@@ -293,14 +307,14 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
 #ifdef EQA_LF_H2_NOPREFETCH    // ablation: no patch loads (the ring keeps the first item's rows)
       if (row0 >= 0) return;
 #endif
+      preh_ok = 0;
 #pragma unroll
       for (int i = 0; i < kLhPre; ++i) {
         const int pr = h_pr[i], px = h_px[i];
         const int gy = it.gy0 + row0 + pr, gx = it.gx0 + px;
         const bool ok = live && pr < nrows && gy < H0 && gx < W0;
-        const unsigned off = ok ? (unsigned)((((it.img * H0 + gy) * (size_t)W0 + gx) * 3) * 4) : 0xfffffff0u;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) preh[i][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off, c * 4, 0));
+        preh_ok |= ok ? 1u << i : 0u;
+        lf_fetch_pixel(preh[i], x, (unsigned)((((it.img * H0 + gy) * (size_t)W0 + gx) * 3) * 4), ok);
       }
     }
   };
@@ -316,7 +330,7 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
           _Float16 hi[3], lo[3];
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
-            const float v = preh[i][c] * x_scale;
+            const float v = lf_pixel_or_zero(preh[i][c], (preh_ok >> i) & 1u) * x_scale;
             hi[c] = (_Float16)v;
             lo[c] = (_Float16)(v - (float)hi[c]);
           }

@@ -53,7 +53,8 @@ __device__ __forceinline__ float lf_pixel_or_zero(float v, bool ok) { return ok 
 
 #ifdef EQA_LF_CLOCK
 // Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of five waves ([8 k .. 8 k + 7], k = slot:
-// waves 8, 1, 0, 6, 11), and HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD) -- tools/kbench_lift_fft.py.
+// waves 8, 1, 0, 6, 11), HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD), and 1 + EQA_LF_H2_DEAL of the h2
+// kernel ([63]: whether wave 6 convolves) -- tools/kbench_lift_fft.py.
 __device__ unsigned long long g_lf_clock[64];
 __device__ __forceinline__ int lf_clock_slot(int wave) { return wave == 8 ? 0 : wave == 1 ? 1 : wave == 0 ? 2 : wave == 6 ? 3 : wave == 11 ? 4 : -1; }
 #define LF_CLOCK_BEGIN() const bool lfc_on = blockIdx.x == 0 && (threadIdx.x & 63) == 0 && lf_clock_slot(wave) >= 0; \
@@ -121,17 +122,72 @@ __device__ __forceinline__ LfItem lf_item(unsigned work, int ngrp, int TY, int T
 //   kConv  waves 6..11: the convolution, 16 tile rows per sub-phase.  Waves w and w + 4 share a SIMD: 6 | 10 and 7 | 11 take 3 + 2 rows,
 //          8 and 9 (alone on their SIMDs) three each
 //   tail   all twelve waves: the row transforms (four consecutive rows x 16 channels per wave), then the column read (waves 0..5)
-// FORM 2 deals them differently: waves 0..5 kCols; waves 8..11 kConv, one per SIMD (waves w, w + 4, w + 8 of a block share a SIMD:
-// HW_REG_HW_ID, profiles/r07/wave_simd.txt), nine of a sub-phase's 36 tiles each; waves 6 and 7 kRowp; waves 6..11 stage the
-// patches (lf_h2_rows: who transforms which rows).
-enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2 only): waves 6, 7 -- staging and row transforms, no convolution
+// FORM 2 deals them differently: waves 0..5 kCols; waves 6..11 kConv AND the patch staging, six of a sub-phase's 36 tiles each (half a
+// tile column).  Waves w, w + 4, w + 8 of a block share a SIMD (HW_REG_HW_ID, profiles/r07/wave_simd.txt): SIMDs 2 and 3 carry TWO
+// convolution waves (6 | 10, 7 | 11), which cover each other's window reads and epilogues on the matrix pipe (48 tiles per item in 17 k
+// cycles, where a wave alone takes 15 k for 24: profiles/r14); waves 8 and 9 are alone on theirs.  No row pass beside the convolution:
+// all twelve run in the tail, one per wave (lf_h2_run: who convolves what; lf_h2_rows: who transforms which rows).
+// EQA_LF_H2_DEAL = 0 is the dealing of profiles/r07 .. r13: waves 8..11 kConv, one per SIMD, nine tiles each; waves 6 and 7 kRowp.
+enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2, EQA_LF_H2_DEAL = 0 only): waves 6, 7 -- staging and row transforms, no convolution
 
-// FORM 2's row transforms.  Sub-phase s = 1..3 (waves 6, 7): a bit mask of the passes k (tile rows 12 (s - 1) + 4 k .. + 3) the
-// wave does beside the convolution; s = 4, the tail (any non-convolution wave): the first row of its pass, or -1.  The convolution
+// FORM 2's row transforms (the dealings are listed below; this paragraph: EQA_LF_H2_DEAL = 0).  Sub-phase s = 1..3 (waves 6, 7): a bit
+// mask of the passes k (tile rows 12 (s - 1) + 4 k .. + 3) the wave does beside the convolution; s = 4, the tail (any
+// non-convolution wave): the first row of its pass, or -1.  The convolution
 // waves are the critical path of a sub-phase, and a row pass takes ~2.4 k cycles of the ~5 k of theirs: one pass per wave and
 // sub-phase fits beside them, two do not (profiles/r07).  So the third pass of every sub-phase waits for the tail, which then has
 // six passes on six waves, at most two per SIMD (waves w, w + 4, w + 8 share one).
-#ifdef EQA_LF_H2_ROWS_IN_SUB   // variant: the third pass alternates between waves 6 and 7, the tail keeps rows 36..47 (1.08 ms, not 1.02)
+//
+// FORM 2's convolution dealing.  A sub-phase is 36 tiles, 3 tile columns x 12 rows; a RUN is what one call of conv_col_h convolves:
+// kLhRun0 rows down one tile column, then kLhRun1 rows down another (0: the run never leaves its column).  The shape is a compile-time
+// constant, one per dealing, so the convolution code exists once; lf_h2_run says where the run of a wave lies (rows counted from the
+// sub-phase's first), the static_assert below that every tile is taken exactly once.
+//   EQA_LF_H2_DEAL = 1  SIX convolution waves 6..11, half a tile column (six tiles) each, no run crosses a column.  Waves 6 | 10 and
+//                       7 | 11 share a SIMD and cover each other's window reads and epilogues; 8 and 9 are alone on theirs.  No row
+//                       pass beside the convolution: all twelve wait for the tail, one per wave (the fp32 form's tail).
+//   EQA_LF_H2_DEAL = 0  FOUR convolution waves 8..11, one per SIMD, nine tiles each in column-major order (tile n: column n / 12, row
+//                       n % 12): wave 8 column 0 rows 0..8, wave 11 column 2 rows 3..11; waves 9 and 10 three rows at the end / start of a
+//                       column, then six of the middle column.  Waves 6, 7: kRowp (profiles/r07 .. r13).
+#ifndef EQA_LF_H2_DEAL
+#define EQA_LF_H2_DEAL 1
+#endif
+constexpr int kLhDeal = EQA_LF_H2_DEAL;
+constexpr int kLhRun0 = kLhDeal == 0 ? 3 : 6, kLhRun1 = kLhDeal == 0 ? 6 : 0;
+constexpr int kLhFirstConv = kLhDeal == 0 ? 8 : 6;     // waves kLhFirstConv..11: kConv; waves 6 .. kLhFirstConv - 1: kRowp
+constexpr bool kLhConvRowsInTail = kLhDeal != 0;       // the convolution waves take a row pass of the tail
+struct LfRun { int y0, t0, y1, t1; bool cross; };      // rows y0 .. y0 + kLhRun0 - 1 of column t0, then y1 .. y1 + kLhRun1 - 1 of column t1
+__host__ __device__ constexpr LfRun lf_h2_run(int wave, int /*sub: every sub-phase is dealt alike*/) {
+  if (kLhDeal == 0) {
+    const bool cross = wave == 9 || wave == 10;
+    const int y0 = (wave == 8 || wave == 10) ? 0 : (wave == 9 ? 9 : 3), t0 = (wave == 8 || wave == 9) ? 0 : 2;
+    return LfRun{y0, t0, cross ? (wave == 9 ? 0 : 6) : y0 + 3, cross ? 1 : t0, cross};
+  }
+  const bool lone = wave == 8 || wave == 9;              // column 0: waves 8, 9; column 1: 6 | 10; column 2: 7 | 11
+  const int y0 = ((lone ? wave == 9 : wave >= 10) ? 6 : 0), t0 = lone ? 0 : 1 + (wave & 1);
+  return LfRun{y0, t0, y0 + kLhRun0, t0, false};
+}
+constexpr bool lf_h2_deal_covers() {
+  int n[3][12] = {};
+  for (int sub = 0; sub < 4; ++sub) {
+    for (int w = kLhFirstConv; w < 12; ++w) {
+      const LfRun r = lf_h2_run(w, sub);
+      if (r.cross != (kLhRun1 > 0 && r.t1 != r.t0)) return false;
+      for (int k = 0; k < kLhRun0 + kLhRun1; ++k) {
+        const int y = k < kLhRun0 ? r.y0 + k : r.y1 + k - kLhRun0, t = k < kLhRun0 ? r.t0 : r.t1;
+        if (y < 0 || y >= 12 || t < 0 || t >= 3) return false;
+        ++n[t][y];
+      }
+    }
+  }
+  for (int t = 0; t < 3; ++t)
+    for (int y = 0; y < 12; ++y)
+      if (n[t][y] != 4) return false;
+  return true;
+}
+static_assert(lf_h2_deal_covers(), "FORM 2: a tile of the sub-phase is left to no wave or taken by two");
+
+#if EQA_LF_H2_DEAL != 0        // every row pass in the tail: wave w rows 4 w .. 4 w + 3
+__device__ __forceinline__ int lf_h2_rows(int wave, int s) { return s < 4 ? 0 : 4 * wave; }
+#elif defined(EQA_LF_H2_ROWS_IN_SUB)   // variant: the third pass alternates between waves 6 and 7, the tail keeps rows 36..47 (1.08 ms, not 1.02)
 __device__ __forceinline__ int lf_h2_rows(int wave, int s) {
   if (s < 4) return wave == 6 ? (1 | ((s & 1) ? 4 : 0)) : (wave == 7 ? (2 | ((s & 1) ? 0 : 4)) : 0);
   return wave == 6 ? 36 : wave == 7 ? 40 : wave == 4 ? 44 : -1;
@@ -167,8 +223,7 @@ constexpr int kLpLdsBytes = kLfTileFloats * 4 + kLpPatchB;   // 160,704 bytes
 // back in the epilogue).  Two planes of 8 bytes per pixel are the fp32 patch's bytes + a third, so a sub-phase is TWELVE tile rows (a
 // ring of 16 patch rows; four sub-phases per item, where the three bf16 planes allowed four rows and needed twelve), and twelve
 // matrix instructions of 16 cycles per 16-pixel tile replace 19 of 32 on a datapath the transforms do not share: the convolution
-// waves, not the column waves, stage the patches (the column waves' loads queued behind their own stores: 8.6 k cycles per item),
-// and two of them transform the previous sub-phase's rows; only twelve rows are left for the tail.
+// waves, not the column waves, stage the patches (the column waves' loads queued behind their own stores: 8.6 k cycles per item).
 //   K layout: a chunk = the pixel pair (j - 1 + 2 p, j + 2 p) of output pixel j, i.e. kx = 2 p - 1 (p = 0: weight 0), 2 p; the
 //   pair of p = 0, j = 0 starts 8 bytes in front of the row: the previous ring row's last pixel, and in front of the patch the tile
 //   buffer's last (never written, zeroed once) pad floats -- which is how the patch fits the CU's LDS to the byte.
@@ -548,13 +603,16 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
       asm volatile("" : "+v"(bias4));
     }
   };
-  // Nine tiles of a sub-phase: rows y0 .. y0 + 2 of tile column t0, then rows y1 .. y1 + 5 of tile column t1 (patch row R sits in ring
-  // slot R % 16).  A wave that stays in its column passes y1 = y0 + 3, t1 = t0 and cross = false; one that CROSSES to a new column
-  // re-reads the four rows of its register window that the first column's last row still used (the two behind them come from the
-  // new column already).
-  auto conv_col_h = [&](const LfItem& it, int y0, int t0, int y1, int t1, bool cross) {
+  // One run of a sub-phase (lf_h2_run): rows y0 .. y0 + N0 - 1 of tile column t0, then rows y1 .. y1 + N1 - 1 of tile column t1 (patch
+  // row R sits in ring slot R % 16).  A wave that stays in its column passes y1 = y0 + N0, t1 = t0 and cross = false (N1 = 0: no run
+  // of the dealing leaves its column, and nothing of the second column is compiled); one that CROSSES to a new column re-reads the
+  // four rows of its register window that the first column's last row still used (the two behind them come from the new column
+  // already).
+  auto conv_col_h = [&](const LfItem& it, auto N0, auto N1, int y0, int t0, int y1, int t1, bool cross_) {
     if constexpr (H2) {
-      constexpr int NROWS = 9, SW = 3;
+      constexpr int NROWS = decltype(N0)::value + decltype(N1)::value, SW = decltype(N0)::value;
+      static_assert(SW >= 2 && NROWS >= 2 && NROWS <= kLhSubRows, "a run: at least two rows, at most a tile column of the sub-phase");
+      const bool cross = NROWS > SW && cross_;
 #ifdef EQA_LF_H2_NOCONV    // ablation: the convolution waves without their convolution (the tile keeps what it held)
       return;
 #endif
@@ -804,15 +862,13 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
             cur_grp = it.grp;
           }
           if constexpr (H2) {
-            // waves 8..11, one per SIMD: nine of the sub-phase's 36 tiles each, in column-major order (tile n: column n / 12, row n % 12)
-            // -- wave 8 column 0 rows 0..8, wave 11 column 2 rows 3..11; waves 9 and 10 three rows at the end / start of a column, then
-            // six of the middle column (a new column: a new register window).  Waves 6, 7: row transforms of the PREVIOUS
-            // sub-phase's rows (lf_h2_rows)
+            // the convolution waves: their run of the sub-phase's 36 tiles (lf_h2_run).  kRowp (a dealing that leaves waves 6, 7
+            // out of the convolution): row transforms of the PREVIOUS sub-phase's rows (lf_h2_rows)
             if constexpr (ROLE == kConv) {
               const int y = kLhSubRows * sub;
-              const bool cross = wave == 9 || wave == 10;
-              const int ya = y + (wave == 8 || wave == 10 ? 0 : (wave == 9 ? 9 : 3)), ta = wave == 8 || wave == 9 ? 0 : 2;
-              conv_col_h(it, ya, ta, cross ? y + (wave == 9 ? 0 : 6) : ya + 3, cross ? 1 : ta, cross);
+              const LfRun run = lf_h2_run(wave, sub);
+              conv_col_h(it, std::integral_constant<int, kLhRun0>(), std::integral_constant<int, kLhRun1>(), y + run.y0, run.t0, y + run.y1, run.t1,
+                         run.cross);
             } else {
               if (sub > 0) {
                 const int a = lf_h2_rows(wave, sub);
@@ -887,7 +943,8 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
     if constexpr (PIECES) {
       if (live) row_pass(4 * wave);
     } else if constexpr (H2) {
-      if constexpr (ROLE != kConv) {
+      // (a convolution wave's pass runs behind its last run: of the convolution only wh and bias4 are live beside it)
+      if constexpr (ROLE != kConv || kLhConvRowsInTail) {
         const int a = lf_h2_rows(wave, NSUB);
         if (live && a >= 0) row_pass(a);
       }
@@ -970,8 +1027,11 @@ __global__ __launch_bounds__(kLfThreads) void lift5_fft48_fused_h2_kernel(const 
                                                                            int nxbound, float w_scale) {
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (w < 6) lift5_fft48_body<kCols, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
-  else if (w >= 8) lift5_fft48_body<kConv, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
-  else lift5_fft48_body<kRowp, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
+  else if (w >= kLhFirstConv) lift5_fft48_body<kConv, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
+  else if constexpr (kLhFirstConv > 6) lift5_fft48_body<kRowp, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
+#ifdef EQA_LF_CLOCK
+  if (blockIdx.x == 0 && threadIdx.x == 0) g_lf_clock[63] = 1 + kLhDeal;    // tools/kbench_lift_fft.py: what wave 6 does
+#endif
 }
 
 // |x| maxima in EQA_LIFT5_DCMAX_SLOTS slots (one per block; the consumer takes the largest): the bound FORM 2 scales its pixels by

@@ -89,8 +89,10 @@ def main():
         items = max(1, (M * (C // 16) + 255) // 256) if M * (C // 16) >= 256 else 1
         hw = [out[40 + w] for w in range(12)]
         simd = {w: (hw[w] >> 4) & 3 for w in range(12)} if any(hw) else {}
+        # [63]: 1 + EQA_LF_H2_DEAL of the h2 kernel (older builds: 0) -- from dealing 1 on wave 6 convolves
+        wave6 = "convolution wave 6" if form == "h2" and out[63] >= 2 else "row-transform wave 6"
         for base, w, who in ((0, 8, "convolution wave 8"), (8, 1, "column wave 1"), (16, 0, "column wave 0 (packed)"),
-                             (24, 6, "row-transform wave 6"), (32, 11, "convolution wave 11")):
+                             (24, 6, wave6), (32, 11, "convolution wave 11")):
             tot = sum(out[base:base + 8])
             if tot == 0:
                 continue

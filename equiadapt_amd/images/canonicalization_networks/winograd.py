@@ -1,4 +1,5 @@
-"""Winograd F(m x m, 5x5) convolution for the 5x5 regular->regular layers of the canonicalization network (inference).
+"""Winograd F(m x m, 5x5) convolution for the 5x5 regular->regular layers of the canonicalization network: the inference
+forward, and `Conv5x5Function` with both gradients for training wherever the FFT convolution does not apply.
 
 Direct convolution spends 25 multiplies per output and channel pair.  Cook-Toom with N = m + 4 points per axis needs
 N*N per m x m output tile:  m = 2, points {0, 1, -1, 2, -2, inf}: 36/4 = 9 per output;  m = 4, points
@@ -14,6 +15,11 @@ fp32), so the only extra rounding at run time is in the two transforms and the P
 arithmetic (tests/test_abi_and_host.py checks the matrices below in rational arithmetic); in fp32, against an fp64
 convolution with 256 channels: m = 2: 7e-6 of max|y|, m = 4: 9e-6 (direct fp32: 3e-7) --
 tests/test_gpu_parity.py::test_winograd_conv_matches_direct bounds both by 2e-5.
+The gradients run on the same kernels (d_x: the convolution of the zero-padded dy with the flipped, transposed bank; d_bank:
+dU[a] = V[:, a]^T (A dY A^T)[:, a] over all tiles, folded back as G^T dU G in fp64).  Against fp64 autograd on an MI355X, 32 - 320
+channels, maps of 12 x 12 to 36 x 44, both tile sizes: d_bank 4.3e-6 ... 2.9e-5 of its largest entry (its sum runs over every tile
+of the batch), d_x 2.2e-6 ... 9.9e-6, that is 0.4 - 2.8 x / 0.7 - 1.9 x what torch's fp32 CPU evaluation of the same chain gives;
+tests/test_gpu_winograd_backward_fp64.py holds each kernel and step to 4 x that evaluation's worst (profiles/r15/).
 m = 4 is used whenever 4 divides H-4 and W-4, else m = 2.  Images are processed in chunks to bound the size of V and M.
 """
 import os

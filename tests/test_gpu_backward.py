@@ -192,7 +192,8 @@ def test_escnn_training_fast_path_matches_module_path(dev, size, monkeypatch):
     """ESCNNEquivariantNetwork in train(): the Winograd / window-sum autograd path vs the plain module sequence
     (F.conv2d + BatchNorm3d + group_pool through autograd) with the same weights: activations, every parameter gradient, the
     input gradient and the batch-norm running statistics.  size 32 exercises F(4x4,5x5), size 30 F(2x2,5x5), size 96 (batch 9:
-    36 tiles) the FFT convolution in the forward pass with the Winograd kernels in the backward pass."""
+    36 tiles) the FFT convolution in the forward pass with the Winograd kernels in the backward pass.
+    (The Winograd gradient kernels on their own, against fp64 and 40 - 100 x tighter: tests/test_gpu_winograd_backward_fp64.py.)"""
     import copy
 
     import equiadapt_amd as ea

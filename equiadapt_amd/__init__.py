@@ -38,6 +38,7 @@ from equiadapt_amd.images.canonicalization_networks import (  # noqa: F401
     ConvNetwork,
     CustomEquivariantNetwork,
     ESCNNEquivariantNetwork,
+    ESCNNSteerableNetwork,
     RotationEquivariantConv,
     RotationEquivariantConvLift,
     RotoReflectionEquivariantConv,
@@ -76,7 +77,7 @@ from equiadapt_amd.common import basecanonicalization  # noqa: E402,F401  (the s
 __all__ = [
     "BaseCanonicalization", "ContinuousGroupCanonicalization", "ContinuousGroupImageCanonicalization",
     "ContinuousGroupPointcloudCanonicalization", "ConvNetwork", "CustomEquivariantNetwork", "DiscreteGroupCanonicalization",
-    "DiscreteGroupImageCanonicalization", "ESCNNEquivariantNetwork", "EquivariantPointcloudCanonicalization",
+    "DiscreteGroupImageCanonicalization", "ESCNNEquivariantNetwork", "ESCNNSteerableNetwork", "EquivariantPointcloudCanonicalization",
     "GroupEquivariantImageCanonicalization", "IdentityCanonicalization", "OptimizedGroupEquivariantImageCanonicalization",
     "OptimizedSteerableImageCanonicalization", "RotationEquivariantConv", "RotationEquivariantConvLift",
     "RotoReflectionEquivariantConv", "RotoReflectionEquivariantConvLift", "SteerableImageCanonicalization", "VNBatchNorm",

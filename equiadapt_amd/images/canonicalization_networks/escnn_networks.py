@@ -34,6 +34,7 @@ from equiadapt_amd.images.canonicalization_networks.pooling import (
     group_pool,
     window_sums_to_activations,
 )
+from equiadapt_amd.images.canonicalization_networks.steerable_networks import ESCNNSteerableNetwork  # noqa: F401  (reference: same module)
 
 
 class _InnerBatchNorm(nn.BatchNorm3d):

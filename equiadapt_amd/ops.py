@@ -996,3 +996,54 @@ def rigid_rows(x: torch.Tensor, R: torch.Tensor, t: Optional[torch.Tensor], inve
         st = lib.eqa_rigid_rows(x.data_ptr(), R.data_ptr(), p_t, out.data_ptr(), x.shape[0], int(inverse), _stream())
     _lib.check(st, "eqa_rigid_rows")
     return out
+
+
+FOURIER_FIELD_DIM = 9   # channels of a band-limited SO(2) field: a_0, (Re, Im) c_1..c_4 (csrc/fourier_act.hip)
+
+
+def _fourier_args(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], what: str):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError(f"{what} expects a channels-last fp32 (B, 9 * fields, H, W) tensor on the device")
+    B, C, H, W = x.shape
+    if C == 0 or C % FOURIER_FIELD_DIM:
+        raise ValueError(f"{what}: {C} channels are not a whole number of 9-channel fields")
+    fields = C // FOURIER_FIELD_DIM
+    scale, p_scale = _opt(scale, "scale", torch.float32)
+    shift, p_shift = _opt(shift, "shift", torch.float32)
+    if scale is not None and tuple(scale.shape) != (fields, 5):
+        raise ValueError(f"{what}: scale must be (fields, 5) = ({fields}, 5), got {tuple(scale.shape)}")
+    if shift is not None and tuple(shift.shape) != (fields,):
+        raise ValueError(f"{what}: shift must be (fields,) = ({fields},), got {tuple(shift.shape)}")
+    return B * H * W, fields, (scale, shift), p_scale, p_shift
+
+
+def fourier_elu(x: torch.Tensor, scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FourierELU (16 samples, frequencies 0..4) of scale * x + shift on a channels-last (B, 9 * fields, H, W) map, one pass
+    (eqa_fourier_elu_fwd).  scale:(fields, 5) per field and frequency, shift:(fields,) on a_0; None: ones / zeros."""
+    lib = _lib.load()
+    npix, fields, keep, p_scale, p_shift = _fourier_args(x, scale, shift, "fourier_elu")
+    y = torch.empty_like(x)
+    if npix == 0:
+        return y
+    with torch.cuda.device(x.device), _timed("fourier_elu"):
+        st = lib.eqa_fourier_elu_fwd(x.data_ptr(), p_scale, p_shift, y.data_ptr(), npix, fields, _stream())
+    _lib.check(st, "eqa_fourier_elu_fwd")
+    return y
+
+
+def fourier_elu_bwd(x: torch.Tensor, dy: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                    shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d/dx of `fourier_elu` (eqa_fourier_elu_bwd): the samples are recomputed from x, the scale is applied inside."""
+    lib = _lib.load()
+    npix, fields, keep, p_scale, p_shift = _fourier_args(x, scale, shift, "fourier_elu_bwd")
+    if not (isinstance(dy, torch.Tensor) and dy.is_cuda and dy.dtype == torch.float32 and dy.shape == x.shape
+            and dy.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError("fourier_elu_bwd expects dy channels-last fp32 on the device, shaped like x")
+    dx = torch.empty_like(x)
+    if npix == 0:
+        return dx
+    with torch.cuda.device(x.device), _timed("fourier_elu_bwd"):
+        st = lib.eqa_fourier_elu_bwd(x.data_ptr(), p_scale, p_shift, dy.data_ptr(), dx.data_ptr(), npix, fields, _stream())
+    _lib.check(st, "eqa_fourier_elu_bwd")
+    return dx

@@ -791,6 +791,21 @@ int eqa_gram_schmidt_bwd(const float* v, const float* grad_out, float* grad_v, i
 int eqa_modified_gram_schmidt(const float* v, float* out, int B, void* stream);
 int eqa_rigid_rows(const float* x, const float* R, const float* t, float* out, int M, int mode, void* stream);
 
+/*
+ * FourierELU over band-limited SO(2) fields, fused with a per-field affine map (ESCNNSteerableNetwork: the hidden activation and,
+ * in eval mode, the field norm in front of it; reference network: escnn_networks.py:120-224, e2cnn FourierELU with N = 16 over
+ * irreps 0..4).  x, y, dy, dx: channels-last (npix, 9 * fields) fp32, 16-byte aligned; channel 9 c + j is coefficient j of field c:
+ * j = 0 -> a_0, j = 2m-1 / 2m -> Re / Im c_m (m = 1..4), f(phi) = a_0 + sum_m sqrt(2) (Re c_m cos m phi + Im c_m sin m phi).
+ *   eqa_fourier_elu_fwd   y = A^T ELU(A u) / 16,  u = scale (.) x + shift,  A:(16, 9) the samples of f at phi_i = 2 pi i / 16
+ *   eqa_fourier_elu_bwd   dx = scale (.) A^T [ELU'(A u) (.) (A dy / 16)]   (u recomputed from x; y is not needed)
+ * scale:(fields, 5) per field and frequency, or NULL (ones); shift:(fields) added to a_0 only, or NULL (zeros).
+ * NULL x / y / dy / dx, npix <= 0 or fields <= 0: EQA_ERR_INVALID_ARG; misaligned maps: EQA_ERR_UNSUPPORTED.  No atomics: two
+ * launches on the same input give the same bits.  Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_fourier_elu_fwd(const float* x, const float* scale, const float* shift, float* y, long long npix, int fields, void* stream);
+int eqa_fourier_elu_bwd(const float* x, const float* scale, const float* shift, const float* dy, float* dx, long long npix, int fields,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

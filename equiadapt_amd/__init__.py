@@ -58,6 +58,7 @@ from equiadapt_amd.images.utils import (  # noqa: F401
     rotate_points,
 )
 from equiadapt_amd.nbody.canonicalization.euclidean_group import EuclideanGroupNBody  # noqa: F401
+from equiadapt_amd.nbody.canonicalization_networks import VNDeepSets  # noqa: F401
 from equiadapt_amd.pointcloud.canonicalization.continuous_group import (  # noqa: F401
     ContinuousGroupPointcloudCanonicalization,
     EquivariantPointcloudCanonicalization,
@@ -85,7 +86,7 @@ __all__ = [
     "custom_group_equivariant_layers", "custom_nonequivariant_networks", "equivariant_networks", "escnn_networks",
     "get_action_on_image_features", "get_graph_feature_cross", "gram_schmidt",
     # not in the reference's __all__, part of this package's surface
-    "EuclideanGroupNBody", "flip_boxes", "flip_masks", "roll_by_gather", "rotate_boxes", "rotate_masks", "rotate_points",
+    "EuclideanGroupNBody", "VNDeepSets", "flip_boxes", "flip_masks", "roll_by_gather", "rotate_boxes", "rotate_masks", "rotate_points",
 ]
 
 __version__ = "0.1.0"

@@ -3,8 +3,8 @@
 Reference: equiadapt/nbody/canonicalization/euclidean_group.py:8-157.  Same API: ``forward(nodes, **kwargs)`` with the
 keyword arguments ``loc, edges, vel, edge_attr, charges`` in that order, ``canonicalize`` returning
 ``(canonical_loc, canonical_vel)``, ``invert_canonicalization`` mapping predicted locations back (``x R + t``).
-The canonicalization network (``VNDeepSets`` in the reference, which needs torch_scatter) is any module returning
-``(rotation_vectors (M,3,3), translation_vectors (M,3))``; the rigid actions and the modified Gram-Schmidt run as HIP kernels
+The canonicalization network is ``equiadapt_amd.nbody.VNDeepSets`` (the reference's network of that name, one launch on the
+device) or any module returning ``(rotation_vectors (M,3,3), translation_vectors (M,3))``; the rigid actions and the modified Gram-Schmidt run as HIP kernels
 (forward only -- n-body training keeps the op-by-op path, selected automatically when autograd is recording).
 """
 from typing import Any, Dict, List, Optional, Tuple, Union

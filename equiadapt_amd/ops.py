@@ -1047,3 +1047,108 @@ def fourier_elu_bwd(x: torch.Tensor, dy: torch.Tensor, scale: Optional[torch.Ten
         st = lib.eqa_fourier_elu_bwd(x.data_ptr(), p_scale, p_shift, dy.data_ptr(), dx.data_ptr(), npix, fields, _stream())
     _lib.check(st, "eqa_fourier_elu_bwd")
     return dx
+
+
+VNDEEPSETS_WIDTHS = (8, 16, 32)   # hidden widths the kernels are compiled for (csrc/nbody.hip); the caller zero-pads others
+VNDEEPSETS_MAX_HIDDEN = 32
+VNDEEPSETS_MAX_LAYERS = 8         # == kMaxLayers
+NBODY_EDGES_OK = 4            # eqa_nbody_adjacency's flag when every edge stays inside a system and node M-1 has an incoming one
+
+
+def nbody_adjacency(rows: torch.Tensor, cols: torch.Tensor, systems: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Edge list (rows = sources, cols = targets; int64) of `systems` 5-body systems -> (adj (systems, 5, 5) int32 in-edge counts
+    [system][target][source], flag (1,) int32: NBODY_EDGES_OK iff the list suits the fused VNDeepSets kernels)."""
+    lib = _lib.load()
+    rows = _need(rows, "rows", torch.int64)
+    cols = _need(cols, "cols", torch.int64)
+    if rows.dim() != 1 or rows.shape != cols.shape or rows.numel() == 0:
+        raise ValueError("nbody_adjacency expects two non-empty index vectors of one length")
+    buf = torch.zeros(systems * 25 + 1, dtype=torch.int32, device=rows.device)      # one zero fill for the counts and the flag
+    adj, flag = buf[:-1].view(systems, 5, 5), buf[-1:]
+    with torch.cuda.device(rows.device), _timed("nbody_adjacency"):
+        st = lib.eqa_nbody_adjacency(rows.data_ptr(), cols.data_ptr(), rows.numel(), systems, adj.data_ptr(), flag.data_ptr(), _stream())
+    _lib.check(st, "eqa_nbody_adjacency")
+    return adj, flag
+
+
+def _vndeepsets_args(loc, vel, charges, adj, packed, hidden, layers, features):
+    loc = _need(loc, "loc")
+    M = loc.shape[0]
+    if loc.dim() != 2 or loc.shape[1] != 3 or M == 0 or M % 5:
+        raise ValueError(f"loc must be (5 * systems, 3), got {tuple(loc.shape)}")
+    vel, p_vel = _opt(vel, "vel", torch.float32)
+    charges, p_ch = _opt(charges, "charges", torch.float32)
+    if vel is not None and tuple(vel.shape) != (M, 3):
+        raise ValueError(f"vel must be ({M}, 3), got {tuple(vel.shape)}")
+    if charges is not None and charges.numel() != M:
+        raise ValueError(f"charges must hold one value per node ({M}), got {tuple(charges.shape)}")
+    adj = _need(adj, "adj", torch.int32)
+    if tuple(adj.shape) != (M // 5, 5, 5):
+        raise ValueError(f"adj must be ({M // 5}, 5, 5), got {tuple(adj.shape)}")
+    packed = _need(packed, "params")
+    n = _lib.load().eqa_vndeepsets_param_count(hidden, layers, features)
+    if packed.dim() != 1 or packed.numel() != n:
+        raise ValueError(f"the packed parameters must be a vector of {n} values, got {tuple(packed.shape)}")
+    return loc, vel, charges, adj, packed, p_vel, p_ch, M
+
+
+def vndeepsets_fwd(loc, vel, charges, adj, packed, *, hidden, layers, features, softplus, slope, layer_mean, final_mean,
+                   canon_translation) -> Tuple[torch.Tensor, torch.Tensor]:
+    """VNDeepSets in one launch (eqa_vndeepsets_fwd): (rotation_vectors (M, 3, 3), translation_vectors (M, 3)).  No autograd."""
+    lib = _lib.load()
+    loc, vel, charges, adj, packed, p_vel, p_ch, M = _vndeepsets_args(loc, vel, charges, adj, packed, hidden, layers, features)
+    rot = torch.empty(M, 3, 3, dtype=torch.float32, device=loc.device)
+    trans = torch.empty(M, 3, dtype=torch.float32, device=loc.device)
+    with torch.cuda.device(loc.device), _timed("vndeepsets_fwd"):
+        st = lib.eqa_vndeepsets_fwd(loc.data_ptr(), p_vel, p_ch, adj.data_ptr(), packed.data_ptr(), rot.data_ptr(), trans.data_ptr(),
+                                    M // 5, hidden, layers, features, int(softplus), slope, int(layer_mean), int(final_mean),
+                                    int(canon_translation), _stream())
+    _lib.check(st, "eqa_vndeepsets_fwd")
+    return rot, trans
+
+
+def vndeepsets_train_fwd(loc, vel, charges, adj, packed, mask, *, hidden, layers, features, softplus, slope, layer_mean, final_mean,
+                         canon_translation) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """As `vndeepsets_fwd`, with dropout by the given factors mask:(layers, M, 3, hidden) (None: none); also returns the inputs of
+    layers 1 .. layers-1, (layers - 1, M, 3, hidden), which `vndeepsets_bwd` needs."""
+    lib = _lib.load()
+    loc, vel, charges, adj, packed, p_vel, p_ch, M = _vndeepsets_args(loc, vel, charges, adj, packed, hidden, layers, features)
+    mask, p_mask = _opt(mask, "mask", torch.float32)
+    if mask is not None and tuple(mask.shape) != (layers, M, 3, hidden):
+        raise ValueError(f"mask must be ({layers}, {M}, 3, {hidden}), got {tuple(mask.shape)}")
+    rot = torch.empty(M, 3, 3, dtype=torch.float32, device=loc.device)
+    trans = torch.empty(M, 3, dtype=torch.float32, device=loc.device)
+    saved = torch.empty(layers - 1, M, 3, hidden, dtype=torch.float32, device=loc.device)
+    with torch.cuda.device(loc.device), _timed("vndeepsets_train_fwd"):
+        st = lib.eqa_vndeepsets_train_fwd(loc.data_ptr(), p_vel, p_ch, adj.data_ptr(), packed.data_ptr(), p_mask,
+                                          saved.data_ptr() if layers > 1 else None, rot.data_ptr(), trans.data_ptr(), M // 5, hidden,
+                                          layers, features, int(softplus), slope, int(layer_mean), int(final_mean),
+                                          int(canon_translation), _stream())
+    _lib.check(st, "eqa_vndeepsets_train_fwd")
+    return rot, trans, saved
+
+
+def vndeepsets_bwd(loc, vel, charges, adj, packed, mask, saved, grad_rot, grad_trans, *, hidden, layers, features, softplus, slope,
+                   layer_mean, final_mean, canon_translation) -> torch.Tensor:
+    """Per-block partial sums (blocks, n_params) of the packed parameters' gradient (eqa_vndeepsets_bwd); `.sum(0)` is the gradient."""
+    lib = _lib.load()
+    loc, vel, charges, adj, packed, p_vel, p_ch, M = _vndeepsets_args(loc, vel, charges, adj, packed, hidden, layers, features)
+    mask, p_mask = _opt(mask, "mask", torch.float32)
+    if mask is not None and tuple(mask.shape) != (layers, M, 3, hidden):
+        raise ValueError(f"mask must be ({layers}, {M}, 3, {hidden}), got {tuple(mask.shape)}")
+    saved = _need(saved, "saved")
+    if tuple(saved.shape) != (layers - 1, M, 3, hidden):
+        raise ValueError(f"saved must be ({layers - 1}, {M}, 3, {hidden}), got {tuple(saved.shape)}")
+    grad_rot = _need(grad_rot, "grad_rot")
+    grad_trans = _need(grad_trans, "grad_trans")
+    if tuple(grad_rot.shape) != (M, 3, 3) or tuple(grad_trans.shape) != (M, 3):
+        raise ValueError(f"grad_rot / grad_trans must be ({M}, 3, 3) / ({M}, 3), got {tuple(grad_rot.shape)} / {tuple(grad_trans.shape)}")
+    blocks = lib.eqa_vndeepsets_bwd_blocks(M // 5)
+    partial = torch.empty(blocks, packed.numel(), dtype=torch.float32, device=loc.device)
+    with torch.cuda.device(loc.device), _timed("vndeepsets_bwd"):
+        st = lib.eqa_vndeepsets_bwd(loc.data_ptr(), p_vel, p_ch, adj.data_ptr(), packed.data_ptr(), p_mask,
+                                    saved.data_ptr() if layers > 1 else None, grad_rot.data_ptr(), grad_trans.data_ptr(),
+                                    partial.data_ptr(), M // 5, hidden, layers, features, int(softplus), slope, int(layer_mean),
+                                    int(final_mean), int(canon_translation), _stream())
+    _lib.check(st, "eqa_vndeepsets_bwd")
+    return partial

@@ -806,6 +806,43 @@ int eqa_fourier_elu_fwd(const float* x, const float* scale, const float* shift, 
 int eqa_fourier_elu_bwd(const float* x, const float* scale, const float* shift, const float* dy, float* dx, long long npix, int fields,
                         void* stream);
 
+/*
+ * VNDeepSets, the n-body canonicalization network (equiadapt/nbody/canonicalization_networks/custom_equivariant_networks.py:13-281),
+ * for systems of 5 bodies: S systems, M = 5 S nodes.  loc, vel:(M,3); charges:(M,1) or (M); vel / charges NULL when the feature
+ * string does not use them.  features: bit 0 = velocity, bit 1 = angular momentum, bit 2 = charge ("p" 0, "pv" 1, "pva" 3,
+ * "pvc" 5, "pvac" 7).  H = 8, 16 or 32, the compiled widths (the caller zero-pads a hidden_dim in between to the next one: channels
+ * with zero weights and biases stay exactly zero), L = num_layers <= 8; anything else: EQA_ERR_UNSUPPORTED.  softplus: 0 = the mask form
+ * (VNLeakyReLU with negative slope `slope`; "relu" is slope 0), 1 = VNSoftplus.  layer_mean / final_mean: 1 = "mean", 0 = "sum".
+ * params: every parameter in the order of the module's parameters(), flattened: per layer identity_linear.weight (H,Cin), .bias (H),
+ * pooling_linear.weight (H,Cin), .bias (H), map_to_dir.weight (H,H), then output_layer.weight (4,H), .bias (4); Cin = the number
+ * of features for layer 0, H afterwards.  eqa_vndeepsets_param_count gives the length.
+ *   eqa_nbody_adjacency      rows, cols:(E) int64 edge list (source, target) -> adj:(S,5,5) int32, adj[s][i][j] = edges from
+ *                            body j to body i of system s (multi-edges and self-loops counted; integer atomics, order-free);
+ *                            *flag |= 1 an index outside [0, M), |= 2 an edge between two systems, |= 4 node M-1 has an incoming
+ *                            edge.  adj and flag must be zero on entry; the edge list suits the kernels below iff *flag == 4.
+ *   eqa_vndeepsets_fwd       the whole network in one launch: rot:(M,3,3) rotation vectors, trans:(M,3) translation vectors
+ *                            (the output layer's 4th column if canon_translation, else 0, plus the system's pooled position)
+ *   eqa_vndeepsets_train_fwd the same, with dropout by a given mask:(L,M,3,H) of factors (NULL: none), keeping the inputs of layers
+ *                            1 .. L-1 in saved:(L-1,M,3,H) (unused for L = 1)
+ *   eqa_vndeepsets_bwd       grad_rot:(M,3,3), grad_trans:(M,3) -> partial:(eqa_vndeepsets_bwd_blocks(S), n_params), whose sum
+ *                            over rows is the gradient of the packed parameters; softplus = 1: EQA_ERR_UNSUPPORTED
+ * Plain loads and stores only in the three network kernels: two launches on the same input give the same bits.
+ * Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_vndeepsets_param_count(int H, int L, int features);
+int eqa_vndeepsets_bwd_blocks(int S);
+int eqa_nbody_adjacency(const int64_t* rows, const int64_t* cols, long long E, int S, int32_t* adj, int32_t* flag, void* stream);
+int eqa_vndeepsets_fwd(const float* loc, const float* vel, const float* charges, const int32_t* adj, const float* params, float* rot,
+                       float* trans, int S, int H, int L, int features, int softplus, float slope, int layer_mean, int final_mean,
+                       int canon_translation, void* stream);
+int eqa_vndeepsets_train_fwd(const float* loc, const float* vel, const float* charges, const int32_t* adj, const float* params,
+                             const float* mask, float* saved, float* rot, float* trans, int S, int H, int L, int features,
+                             int softplus, float slope, int layer_mean, int final_mean, int canon_translation, void* stream);
+int eqa_vndeepsets_bwd(const float* loc, const float* vel, const float* charges, const int32_t* adj, const float* params,
+                       const float* mask, const float* saved, const float* grad_rot, const float* grad_trans, float* partial, int S,
+                       int H, int L, int features, int softplus, float slope, int layer_mean, int final_mean, int canon_translation,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

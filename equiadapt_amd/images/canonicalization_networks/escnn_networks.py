@@ -30,8 +30,10 @@ from equiadapt_amd.common.utils import update_running_stats
 from equiadapt_amd.images.canonicalization_networks import fftconv, winograd
 from equiadapt_amd.images.canonicalization_networks.pooling import (
     WindowSumsFunction,
+    WindowSumsLinearFn,
     conv_then_group_pool,
     group_pool,
+    window_grad_table,
     window_sums_to_activations,
 )
 from equiadapt_amd.images.canonicalization_networks.steerable_networks import ESCNNSteerableNetwork  # noqa: F401  (reference: same module)
@@ -81,116 +83,94 @@ class LiftConvFunction(torch.autograd.Function):
         return dx, dbank, None
 
 
+def _moments(s1, s2, n, bn, conv_bias):
+    """Per-field sum and sum of squares (fp64) over n elements -> batch mean and biased variance (fp32), the running statistics updated
+    like nn.BatchNorm3d (momentum, unbiased variance).  The preceding convolution's bias only shifts the mean (it cancels in the
+    normalised output), so it enters the running mean and nowhere else."""
+    mean = s1 / n
+    var = (s2 / n - mean * mean).clamp_min(0.0)
+    with torch.no_grad():
+        full_mean = mean if conv_bias is None else mean + conv_bias.double()
+        update_running_stats(bn, full_mean, var * (n / max(n - 1, 1)))
+    return mean.float(), var.float()
+
+
+def _block_affine(h, weight, bias, bn, E, conv_bias, part):
+    """InnerBatchNorm of the channels-last (B, fields*E, H, W) map h as a per-channel affine map: (mean_c, rstd_c, scale, shift,
+    batch_stats), each vector repeated over the E channels of its field.  Batch statistics per field over (batch, group, space) in
+    fp64, from part -- the (rows, C, 2) fp64 partial sums of h's per-channel sum / sum of squares, when the kernel that produced h
+    took them on the way out (LiftConvFunction with_stats, the FFT convolution's inverse transform) -- or from one pass over h here;
+    a batch-norm in eval mode: its running statistics."""
+    Bn, C, H, W = h.shape
+    Fd = C // E
+    batch_stats = bool(bn.training or bn.running_mean is None)
+    if batch_stats:
+        sums = (ops.inner_bn_stats(h) if part is None else part).sum(0).view(Fd, E, 2).sum(1)              # (fields, 2) fp64
+        mean, var = _moments(sums[:, 0], sums[:, 1], Bn * H * W * E, bn, None if conv_bias is None else conv_bias.detach())
+    else:
+        mean = bn.running_mean if conv_bias is None else bn.running_mean - conv_bias.detach()
+        var = bn.running_var
+    rstd = torch.rsqrt(var + bn.eps)
+    scale = weight.detach() * rstd
+    mean_c, rstd_c, scale, shift = torch.stack([mean, rstd, scale, bias.detach() - mean * scale]).repeat_interleave(E, dim=1)
+    return mean_c, rstd_c, scale, shift, batch_stats                         # (rows of one contiguous (4, C) tensor)
+
+
+def _dropout_draw(p, drop_training):
+    """(p_eff, seed) of the block's dropout mask, a hash of (seed, element index): the seed is drawn from torch's CPU generator, so
+    torch.manual_seed reproduces the mask; no draw where nothing is dropped."""
+    p_eff = float(p) if drop_training else 0.0
+    return p_eff, (int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_eff > 0 else 0)
+
+
+def _block_backward(ctx, g, k=0):
+    """The hidden block's gradients for the eight inputs its two Functions share (h, weight, bias, bn, E, conv_bias, p, drop_training),
+    from what the forward left in ctx.  g, k: the upstream gradient as `ops.inner_bn_bwd_reduce` takes it (k = 0: a channels-last
+    map; k > 0: the window sums' class table)."""
+    h, weight, mean_c, rstd_c, scale, shift = ctx.saved_tensors
+    E = ctx.E
+    Bn, C, H, W = h.shape
+    Fd = C // E
+    part = ops.inner_bn_bwd_reduce(g, h, mean_c, rstd_c, scale, shift, ctx.p, ctx.seed, k)
+    sums = part.sum(0).view(Fd, E, 2).sum(1)                                 # per field: sum g, sum g*xhat
+    dbias, dweight = sums[:, 0].float(), sums[:, 1].float()
+    if ctx.batch_stats:
+        bd = (sums / (Bn * H * W * E)).float().t()                           # per field: mean of g, of g*xhat
+    else:                                                                    # running statistics are constants
+        bd = torch.zeros(2, Fd, device=h.device)
+    a, b, d = torch.cat([(weight * rstd_c.view(Fd, E)[:, 0])[None], bd]).repeat_interleave(E, dim=1)
+    dh = ops.inner_bn_bwd_apply(g, h, mean_c, rstd_c, a, b, d, scale, shift, ctx.p, ctx.seed, k)
+    # With batch statistics the convolution bias cancels in the normalised output (zero gradient).  With running statistics
+    # (frozen batch-norm under autograd) it does not: out = scale * (h + conv_bias - running_mean) + ..., so
+    # d conv_bias = per-field sum of dh, as the op-by-op path and the reference propagate it.
+    # The zero is returned as a tensor, not as None: the reference and the op-by-op path leave an exact-zero .grad on the
+    # bias, which weight decay then acts on and which DistributedDataParallel needs to count the parameter as used.
+    dconv_bias = None
+    if ctx.has_conv_bias and ctx.needs_input_grad[5]:
+        if ctx.batch_stats:
+            dconv_bias = torch.zeros(Fd, dtype=h.dtype, device=h.device)
+        else:
+            dconv_bias = dh.sum(dim=(0, 2, 3), dtype=torch.float64).view(Fd, E).sum(1).float()
+    return dh, dweight, dbias, None, None, dconv_bias, None, None
+
+
 class InnerBnReluDropout(torch.autograd.Function):
     """dropout(relu(InnerBatchNorm(h))) on a channels-last (B, fields*E, H, W) map, forward and backward on the fused
-    kernels of csrc/batchnorm.hip (eqa_bn_*).  Statistics per field over (batch, group, space) in fp64; running statistics
-    updated like nn.BatchNorm3d (momentum, unbiased variance).  The preceding convolution's bias only shifts the mean (it
-    cancels in the normalised output), so it enters the running mean and nowhere else.  The dropout mask is a hash of a
-    seed drawn from torch's CPU generator; the backward recomputes "kept and positive" from h, the affine map and that seed
-    instead of reading y (one map less per pass)."""
+    kernels of csrc/batchnorm.hip (eqa_bn_*): statistics and affine map by `_block_affine`, mask seed by `_dropout_draw`; the
+    backward (`_block_backward`) recomputes "kept and positive" from h, the affine map and that seed instead of reading y (one map
+    less per pass)."""
 
     @staticmethod
     def forward(ctx, h, weight, bias, bn, E, conv_bias, p, drop_training, part=None):
-        """part: (rows, C, 2) fp64 partial sums of h's per-channel sum / sum of squares when the kernel that produced h took them
-        on the way out (LiftConvFunction with_stats, the FFT convolution's inverse transform); None: one pass over h here."""
-        from equiadapt_amd import _lib, ops
-
-        lib = _lib.load()
-        Bn, C, H, W = h.shape
-        Fd = C // E
-        npix = Bn * H * W
-        st = ops._stream()
-        with torch.cuda.device(h.device):
-            if bn.training or bn.running_mean is None:
-                if part is None:
-                    nblk = lib.eqa_bn_partial_blocks(npix)
-                    part = torch.empty((nblk, C, 2), dtype=torch.float64, device=h.device)
-                    _lib.check(lib.eqa_bn_stats_nhwc(h.data_ptr(), part.data_ptr(), npix, C, st), "eqa_bn_stats_nhwc")
-                sums = part.sum(0).view(Fd, E, 2).sum(1)                         # (fields, 2) fp64
-                n = npix * E
-                mean = sums[:, 0] / n
-                var = (sums[:, 1] / n - mean * mean).clamp_min(0.0)
-                full_mean = mean if conv_bias is None else mean + conv_bias.detach().double()
-                update_running_stats(bn, full_mean, var * (n / max(n - 1, 1)))
-                mean, var = mean.float(), var.float()
-            else:
-                mean = bn.running_mean if conv_bias is None else bn.running_mean - conv_bias.detach()
-                var = bn.running_var
-            rstd = torch.rsqrt(var + bn.eps)
-            scale_f = weight.detach() * rstd
-            scale = scale_f.repeat_interleave(E).contiguous()
-            shift = (bias.detach() - mean * scale_f).repeat_interleave(E).contiguous()
-            p_eff = float(p) if drop_training else 0.0
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_eff > 0 else 0
-            y = torch.empty_like(h)
-            _lib.check(lib.eqa_bn_relu_dropout_nhwc(h.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), npix, C, p_eff,
-                                                    seed, st), "eqa_bn_relu_dropout_nhwc")
-        # y is not kept for the backward: "kept and positive" is recomputed from h, scale, shift and the seed
-        ctx.save_for_backward(h, weight, mean.repeat_interleave(E).contiguous(), rstd.repeat_interleave(E).contiguous(), scale, shift)
-        ctx.E, ctx.p, ctx.seed, ctx.batch_stats = E, p_eff, seed, bool(bn.training or bn.running_mean is None)
-        ctx.has_conv_bias = conv_bias is not None
-        return y
+        mean_c, rstd_c, scale, shift, batch_stats = _block_affine(h, weight, bias, bn, E, conv_bias, part)
+        p_eff, seed = _dropout_draw(p, drop_training)
+        ctx.save_for_backward(h, weight, mean_c, rstd_c, scale, shift)       # not y: see above
+        ctx.E, ctx.p, ctx.seed, ctx.batch_stats, ctx.has_conv_bias = E, p_eff, seed, batch_stats, conv_bias is not None
+        return ops.inner_bn_relu_dropout(h, scale, shift, p_eff, seed)
 
     @staticmethod
     def backward(ctx, gy):
-        from equiadapt_amd import _lib, ops
-
-        lib = _lib.load()
-        h, weight, mean_c, rstd_c, scale, shift = ctx.saved_tensors
-        E = ctx.E
-        Bn, C, H, W = h.shape
-        Fd = C // E
-        npix = Bn * H * W
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        st = ops._stream()
-        with torch.cuda.device(h.device):
-            nblk = lib.eqa_bn_partial_blocks(npix)
-            part = torch.empty((nblk, C, 2), dtype=torch.float64, device=h.device)
-            _lib.check(lib.eqa_bn_bwd_reduce_nhwc(gy.data_ptr(), None, h.data_ptr(), mean_c.data_ptr(), rstd_c.data_ptr(), ctx.p,
-                                                  part.data_ptr(), npix, C, scale.data_ptr(), shift.data_ptr(), ctx.seed, st),
-                       "eqa_bn_bwd_reduce_nhwc")
-            sums = part.sum(0).view(Fd, E, 2).sum(1)                             # per field: sum g, sum g*xhat
-            dbias, dweight = sums[:, 0].float(), sums[:, 1].float()
-            n = npix * E
-            a = (weight * rstd_c.view(Fd, E)[:, 0]).repeat_interleave(E).contiguous()
-            if ctx.batch_stats:
-                b = (sums[:, 0] / n).float().repeat_interleave(E).contiguous()
-                d = (sums[:, 1] / n).float().repeat_interleave(E).contiguous()
-            else:                                                                # running statistics are constants
-                b = torch.zeros(C, device=h.device)
-                d = b
-            dh = torch.empty_like(h)
-            _lib.check(lib.eqa_bn_bwd_apply_nhwc(gy.data_ptr(), None, h.data_ptr(), mean_c.data_ptr(), rstd_c.data_ptr(),
-                                                 a.data_ptr(), b.data_ptr(), d.data_ptr(), ctx.p, dh.data_ptr(), npix, C,
-                                                 scale.data_ptr(), shift.data_ptr(), ctx.seed, st), "eqa_bn_bwd_apply_nhwc")
-        # With batch statistics the convolution bias cancels in the normalised output (zero gradient).  With running statistics
-        # (frozen batch-norm under autograd) it does not: out = scale * (h + conv_bias - running_mean) + ..., so
-        # d conv_bias = per-field sum of dh, as the op-by-op path and the reference propagate it.
-        # The zero is returned as a tensor, not as None: the reference and the op-by-op path leave an exact-zero .grad on the
-        # bias, which weight decay then acts on and which DistributedDataParallel needs to count the parameter as used.
-        dconv_bias = None
-        if ctx.has_conv_bias and ctx.needs_input_grad[5]:
-            if ctx.batch_stats:
-                dconv_bias = torch.zeros(Fd, dtype=h.dtype, device=h.device)
-            else:
-                dconv_bias = dh.sum(dim=(0, 2, 3), dtype=torch.float64).view(Fd, E).sum(1).float()
-        return dh, dweight, dbias, None, None, dconv_bias, None, None, None
-
-
-def _window_grad_table(dS: torch.Tensor, H: int, W: int, k: int) -> torch.Tensor:
-    """Backward of the k*k shifted-window sums as a table: a pixel's gradient depends only on the class of its row and of its
-    column (the k-1 top / left border indices, the interior, the k-1 bottom / right ones): (B, C, k, k) -> (B, 2k-1, 2k-1, C) fp32."""
-    nb, dev = k - 1, dS.device
-    if (dS.is_cuda and dS.dtype == torch.float64 and k <= ops.MAX_WINDOW_K and dS.shape[0] <= 65535 and H >= 2 * nb + 1 and W >= 2 * nb + 1
-            and os.environ.get("EQA_WS_TABLE_KERNEL", "1") != "0"):
-        return ops.window_grad_table(dS.contiguous(), H, W)       # rectangle sums from prefix sums: one launch, no library GEMM
-
-    def mask(n):
-        rep = torch.cat([torch.arange(nb), torch.tensor([nb]), torch.arange(n - nb, n)]).to(dev)       # one representative per class
-        u = torch.arange(k, device=dev)
-        return ((u[None, :] <= rep[:, None]) & (rep[:, None] <= u[None, :] + (n - k))).to(dS.dtype)    # (2nb+1, k)
-
-    return torch.einsum("tu,bcuv,sv->btsc", mask(H), dS, mask(W)).float().contiguous()
+        return _block_backward(ctx, gy.contiguous(memory_format=torch.channels_last)) + (None,)
 
 
 class InnerBnReluDropoutWindowSums(torch.autograd.Function):
@@ -199,88 +179,21 @@ class InnerBnReluDropoutWindowSums(torch.autograd.Function):
     kernel loads h (eqa_window_sums_nhwc_act); the backward reads the upstream gradient from the window sums' (2k-1) x (2k-1) class
     table (eqa_bn_bwd_*_wsgrad) instead of an expanded map.  Against InnerBnReluDropout + WindowSumsFunction at the headline shape
     (256 x 88 x 88 x 256): one 2.2 GB map less written and read in the forward, one less written and two fewer reads in the backward
-    (-2.0 ms of the 29.7 ms training step).  Same statistics, same mask, same arithmetic per element."""
+    (-2.0 ms of the 29.7 ms training step).  Same statistics, same mask, same arithmetic per element: everything but the launches
+    is InnerBnReluDropout's."""
 
     @staticmethod
     def forward(ctx, h, weight, bias, bn, E, conv_bias, p, drop_training, k, part=None):
-        from equiadapt_amd import _lib, ops
-
-        lib = _lib.load()
-        Bn, C, H, W = h.shape
-        Fd = C // E
-        npix = Bn * H * W
-        st = ops._stream()
-        with torch.cuda.device(h.device):
-            batch_stats = bool(bn.training or bn.running_mean is None)
-            if batch_stats:
-                if part is None:                                                 # (else: taken by the producer of h, see InnerBnReluDropout)
-                    nblk = lib.eqa_bn_partial_blocks(npix)
-                    part = torch.empty((nblk, C, 2), dtype=torch.float64, device=h.device)
-                    _lib.check(lib.eqa_bn_stats_nhwc(h.data_ptr(), part.data_ptr(), npix, C, st), "eqa_bn_stats_nhwc")
-                sums = part.sum(0).view(Fd, E, 2).sum(1)
-                n = npix * E
-                mean = sums[:, 0] / n
-                var = (sums[:, 1] / n - mean * mean).clamp_min(0.0)
-                full_mean = mean if conv_bias is None else mean + conv_bias.detach().double()
-                update_running_stats(bn, full_mean, var * (n / max(n - 1, 1)))
-                mean, var = mean.float(), var.float()
-            else:
-                mean = bn.running_mean if conv_bias is None else bn.running_mean - conv_bias.detach()
-                var = bn.running_var
-            rstd = torch.rsqrt(var + bn.eps)
-            scale_f = weight.detach() * rstd
-            scale = scale_f.repeat_interleave(E).contiguous()
-            shift = (bias.detach() - mean * scale_f).repeat_interleave(E).contiguous()
-            p_eff = float(p) if drop_training else 0.0
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_eff > 0 else 0
-            S = torch.empty((Bn, C, k, k), dtype=torch.float64, device=h.device)
-            ws = torch.empty((max(lib.eqa_window_sums_nhwc_workspace_bytes(Bn, C, H, k), 4) // 4,), dtype=torch.float32, device=h.device)
-            _lib.check(lib.eqa_window_sums_nhwc_act(h.data_ptr(), scale.data_ptr(), shift.data_ptr(), 1, p_eff, seed, S.data_ptr(),
-                                                    ws.data_ptr(), Bn, C, H, W, k, st), "eqa_window_sums_nhwc_act")
-        ctx.save_for_backward(h, weight, mean.repeat_interleave(E).contiguous(), rstd.repeat_interleave(E).contiguous(), scale, shift)
-        ctx.E, ctx.p, ctx.seed, ctx.batch_stats, ctx.k = E, p_eff, seed, batch_stats, k
-        ctx.has_conv_bias = conv_bias is not None
-        return S
+        mean_c, rstd_c, scale, shift, batch_stats = _block_affine(h, weight, bias, bn, E, conv_bias, part)
+        p_eff, seed = _dropout_draw(p, drop_training)
+        ctx.save_for_backward(h, weight, mean_c, rstd_c, scale, shift)
+        ctx.E, ctx.p, ctx.seed, ctx.batch_stats, ctx.has_conv_bias, ctx.k = E, p_eff, seed, batch_stats, conv_bias is not None, k
+        return ops.window_sums_nhwc_act(h, scale, shift, p_eff, seed, k)
 
     @staticmethod
     def backward(ctx, dS):
-        from equiadapt_amd import _lib, ops
-
-        lib = _lib.load()
-        h, weight, mean_c, rstd_c, scale, shift = ctx.saved_tensors
-        E, k = ctx.E, ctx.k
-        Bn, C, H, W = h.shape
-        Fd = C // E
-        npix = Bn * H * W
-        table = _window_grad_table(dS, H, W, k)
-        st = ops._stream()
-        with torch.cuda.device(h.device):
-            nblk = lib.eqa_bn_partial_blocks(npix)
-            part = torch.empty((nblk, C, 2), dtype=torch.float64, device=h.device)
-            _lib.check(lib.eqa_bn_bwd_reduce_nhwc_wsgrad(table.data_ptr(), h.data_ptr(), mean_c.data_ptr(), rstd_c.data_ptr(), ctx.p,
-                                                         part.data_ptr(), Bn, H, W, C, k, scale.data_ptr(), shift.data_ptr(), ctx.seed, st),
-                       "eqa_bn_bwd_reduce_nhwc_wsgrad")
-            sums = part.sum(0).view(Fd, E, 2).sum(1)
-            dbias, dweight = sums[:, 0].float(), sums[:, 1].float()
-            n = npix * E
-            a = (weight * rstd_c.view(Fd, E)[:, 0]).repeat_interleave(E).contiguous()
-            if ctx.batch_stats:
-                b = (sums[:, 0] / n).float().repeat_interleave(E).contiguous()
-                d = (sums[:, 1] / n).float().repeat_interleave(E).contiguous()
-            else:
-                b = torch.zeros(C, device=h.device)
-                d = b
-            dh = torch.empty_like(h)
-            _lib.check(lib.eqa_bn_bwd_apply_nhwc_wsgrad(table.data_ptr(), h.data_ptr(), mean_c.data_ptr(), rstd_c.data_ptr(), a.data_ptr(),
-                                                        b.data_ptr(), d.data_ptr(), ctx.p, dh.data_ptr(), Bn, H, W, C, k, scale.data_ptr(),
-                                                        shift.data_ptr(), ctx.seed, st), "eqa_bn_bwd_apply_nhwc_wsgrad")
-        dconv_bias = None
-        if ctx.has_conv_bias and ctx.needs_input_grad[5]:
-            if ctx.batch_stats:
-                dconv_bias = torch.zeros(Fd, dtype=h.dtype, device=h.device)
-            else:
-                dconv_bias = dh.sum(dim=(0, 2, 3), dtype=torch.float64).view(Fd, E).sum(1).float()
-        return dh, dweight, dbias, None, None, dconv_bias, None, None, None, None
+        h = ctx.saved_tensors[0]
+        return _block_backward(ctx, window_grad_table(dS, h.shape[-2], h.shape[-1], ctx.k), ctx.k) + (None, None)
 
 
 class _DenseConv(nn.Module):
@@ -592,21 +505,14 @@ class ESCNNEquivariantNetwork(nn.Module):
     # -- training fast path ------------------------------------------------------------------------------------
     @staticmethod
     def _inner_bn(h: torch.Tensor, bn: nn.BatchNorm3d, E: int, conv_bias) -> torch.Tensor:
-        """InnerBatchNorm on a channels-last (B, fields*E, H, W) map: statistics per field over (batch, group, space), fp64
-        accumulation, running statistics updated like nn.BatchNorm3d (momentum, unbiased variance).  The convolution's own
-        bias only shifts the mean (it cancels in the normalised output), so it enters the running mean and nowhere else."""
+        """InnerBatchNorm on a channels-last (B, fields*E, H, W) map, op by op and differentiable by autograd (any device; the
+        reference of the fused kernels' tests): statistics per field over (batch, group, space), fp64 accumulation, `_moments`."""
         Bn, C, H, W = h.shape
         Fd = C // E
         if bn.training or bn.running_mean is None:
-            n = Bn * E * H * W
             s1 = h.sum(dim=(0, 2, 3), dtype=torch.float64).view(Fd, E).sum(1)
             s2 = (h * h).sum(dim=(0, 2, 3), dtype=torch.float64).view(Fd, E).sum(1)
-            mean = s1 / n
-            var = (s2 / n - mean * mean).clamp_min(0.0)
-            with torch.no_grad():
-                full_mean = mean if conv_bias is None else mean + conv_bias.double()
-                update_running_stats(bn, full_mean, var * (n / max(n - 1, 1)))
-            mean, var = mean.float(), var.float()
+            mean, var = _moments(s1, s2, Bn * E * H * W, bn, conv_bias)
         else:
             mean = bn.running_mean if conv_bias is None else bn.running_mean - conv_bias
             var = bn.running_var
@@ -614,63 +520,73 @@ class ESCNNEquivariantNetwork(nn.Module):
         shift = bn.bias - mean * scale
         return h * scale.repeat_interleave(E)[None, :, None, None] + shift.repeat_interleave(E)[None, :, None, None]
 
+    def _train_route(self, li, h, bank, convs, bn):
+        """(conv, with_stats, block) of hidden layer li of the training path on the channels-last activation h, decided from
+        shapes and the EQA_TRAIN_* flags alone: nothing is launched.
+        conv: "wino" | "fftk" | "lift" | "lift_wide" | "lib", in this order of precedence.  with_stats: the convolution takes the
+        block's batch statistics in its epilogue.  block: "fused_tail" (the last hidden block goes straight into the window sums of
+        the linearised final layer: its output is never written) | "fused" | "ops" (op by op, the reference of the fused kernels'
+        tests; also what a library convolution that answers in another layout than channels-last gets)."""
+        conv, kt = convs[li], convs[-1].kernel_size
+        cout, cin = bank.shape[:2]
+        k = conv.kernel_size
+        fused = os.environ.get("EQA_TRAIN_FUSED_BN", "1") != "0"
+        want_stats = (fused and os.environ.get("EQA_TRAIN_EPILOGUE_STATS", "1") != "0" and (bn.training or bn.running_mean is None))
+        lift = self._lift_kernel(conv, bank, h, narrow_unchecked=True)
+        with_stats = False
+        if not conv.lifting and k == 5 and winograd.applicable(h, cin, cout):
+            route, with_stats = "wino", want_stats and winograd.Conv5x5Function.stats_supported(h, bank)
+        elif (not conv.lifting and k != 5
+              and fftconv.applicable_k(h.shape, cin, cout, k, h.device, h.is_contiguous(memory_format=torch.channels_last))):
+            route = "fftk"   # kernel sizes Winograd F(m, 5) does not cover (the tutorial's k = 9): forward and both gradients as FFT convolutions
+        elif lift == "narrow":
+            route, with_stats = "lift", want_stats and ops.lift_conv_stats_supported(h.shape, k, k, cout)
+        else:
+            route = "lift_wide" if lift == "wide" else "lib"
+        OH, OW = h.shape[-2] - k + 1, h.shape[-1] - k + 1                     # (stride 1, no padding: `_training_fast_path_ok`)
+        if (fused and li == len(convs) - 2 and os.environ.get("EQA_TRAIN_FUSED_TAIL", "1") != "0" and kt <= ops.MAX_WINDOW_K
+                and OH > 2 * (kt - 1) and OW > 2 * (kt - 1) and h.shape[0] <= 65535):
+            return route, with_stats, "fused_tail"
+        return route, with_stats, "fused" if fused else "ops"
+
     def _forward_training(self, x: torch.Tensor) -> torch.Tensor:
-        """Same layers as ``self.eqv_network`` + group pooling, with autograd, channels-last: 5x5 regular->regular
-        convolutions through Winograd (``winograd.Conv5x5Function``: forward, d/dx and d/dfilters on the Winograd kernels),
-        the last convolution + group mean as window sums + GEMV (``WindowSumsFunction``), batch-norm / ReLU / dropout as
-        element-wise passes.  Measured on the headline net, B = 256: 353 ms per step through MIOpen -> see HISTORY.md."""
-        mods = list(self.eqv_network)
-        convs = [m for m in mods if hasattr(m, "expanded_weights")]
-        norms = [m for m in mods if isinstance(m, _InnerBatchNorm)]
-        drops = [m for m in mods if isinstance(m, nn.Dropout)]
+        """Same layers as ``self.eqv_network`` + group pooling, with autograd, channels-last.  Per hidden layer `_train_route`
+        decides, the loop body runs the decision: the convolution on the hand-written kernels with both gradients
+        (``winograd.Conv5x5Function`` -- FFT or Winograd --, ``fftconv.ConvKxKFunction``, ``LiftConvFunction``) or the library's, then
+        batch-norm / ReLU / dropout as one fused block (``InnerBnReluDropout``; the last one straight into the window sums:
+        ``InnerBnReluDropoutWindowSums``) or op by op.  The last convolution + group mean are window sums + a GEMV."""
+        convs, norms = self._layers()
+        drops = [m for m in self.eqv_network if isinstance(m, nn.Dropout)]
         E = self.num_group_elements
         h = x.contiguous(memory_format=torch.channels_last)
         tail = convs[-1]
         S = None
-        epilogue_stats = os.environ.get("EQA_TRAIN_FUSED_BN", "1") != "0" and os.environ.get("EQA_TRAIN_EPILOGUE_STATS", "1") != "0"
         for li, (conv, bn, drop) in enumerate(zip(convs[:-1], norms, drops)):
             bank = conv.expanded_weights()
-            part = None          # fp64 partial sums of the block's batch statistics, when the convolution kernel took them
-            lift = self._lift_kernel(conv, bank, h, narrow_unchecked=True)
-            if not conv.lifting and conv.kernel_size == 5 and winograd.applicable(h, bank.shape[1], bank.shape[0]):
-                if (epilogue_stats and (bn.training or bn.running_mean is None) and winograd.Conv5x5Function.stats_supported(h, bank)):
-                    h, part = winograd.Conv5x5Function.apply(h, bank, winograd.tile_for(h), True)
-                else:
-                    h = winograd.Conv5x5Function.apply(h, bank, winograd.tile_for(h))
-            elif (not conv.lifting and conv.kernel_size != 5
-                  and fftconv.applicable_k(h.shape, bank.shape[1], bank.shape[0], conv.kernel_size, h.device,
-                                           h.is_contiguous(memory_format=torch.channels_last))):
-                # kernel sizes Winograd F(m, 5) does not cover (the tutorial's k = 9): forward and both gradients as FFT convolutions
+            route, with_stats, block = self._train_route(li, h, bank, convs, bn)
+            if route == "wino":
+                h = winograd.Conv5x5Function.apply(h, bank, winograd.tile_for(h), with_stats)
+            elif route == "fftk":
                 h = fftconv.ConvKxKFunction.apply(h, bank)
-            elif lift == "narrow":
-                # batch statistics of the norm behind the layer: taken in the convolution's epilogue where the kernel has that form
-                if (epilogue_stats and (bn.training or bn.running_mean is None)
-                        and ops.lift_conv_stats_supported(h.shape, conv.kernel_size, conv.kernel_size, bank.shape[0])):
-                    h, part = LiftConvFunction.apply(h, bank, True)
-                else:
-                    h = LiftConvFunction.apply(h, bank)
-            elif lift == "wide":
-                h = LiftConvFunction.apply(h, bank)          # forward: eqa_lift_conv_wide; filter gradient: the framework's
+            elif route in ("lift", "lift_wide"):     # (wide: forward eqa_lift_conv_wide, filter gradient the framework's)
+                h = LiftConvFunction.apply(h, bank, with_stats)
             else:
                 h = F.conv2d(h, bank.contiguous(memory_format=torch.channels_last))
-            fused = os.environ.get("EQA_TRAIN_FUSED_BN", "1") != "0" and h.is_contiguous(memory_format=torch.channels_last)
-            kt = tail.kernel_size
-            if (fused and li == len(convs) - 2 and os.environ.get("EQA_TRAIN_FUSED_TAIL", "1") != "0" and kt <= ops.MAX_WINDOW_K
-                    and h.shape[-2] > 2 * (kt - 1) and h.shape[-1] > 2 * (kt - 1) and h.shape[0] <= 65535):
-                # the last hidden block goes straight into the window sums of the linearised final layer: its output is never written
-                S = InnerBnReluDropoutWindowSums.apply(h, bn.weight, bn.bias, bn, E, conv.bias, drop.p, drop.training, kt, part)
-            elif fused:
+                if not h.is_contiguous(memory_format=torch.channels_last):
+                    block = "ops"
+            # part: the fp64 partial sums of the block's batch statistics, where the convolution kernel took them
+            h, part = h if with_stats else (h, None)
+            if block == "fused_tail":
+                S = InnerBnReluDropoutWindowSums.apply(h, bn.weight, bn.bias, bn, E, conv.bias, drop.p, drop.training, tail.kernel_size, part)
+            elif block == "fused":
                 h = InnerBnReluDropout.apply(h, bn.weight, bn.bias, bn, E, conv.bias, drop.p, drop.training, part)
-            else:  # op-by-op form of the same block (kept as the reference for the fused kernels' test)
-                h = self._inner_bn(h, bn, E, conv.bias)
-                h = F.dropout(torch.relu(h), drop.p, drop.training)
+            else:
+                h = F.dropout(torch.relu(self._inner_bn(h, bn, E, conv.bias)), drop.p, drop.training)
         k, O = tail.kernel_size, tail.out_channels
         H, W = h.shape[-2:]
         if S is None:
             S = WindowSumsFunction.apply(h, k)                                      # (B, C, k, k) fp64
         weff = tail.expanded_weights().view(O, E, -1).double().sum(0)               # (E, C*k*k), differentiable
-        from equiadapt_amd.images.canonicalization_networks.pooling import WindowSumsLinearFn
-
         if S.is_cuda and S.dtype == torch.float64 and E <= 16 and os.environ.get("EQA_WS_TABLE_KERNEL", "1") != "0":
             act = WindowSumsLinearFn.apply(S.flatten(1), weff, 1.0 / float(O * (H - k + 1) * (W - k + 1)))     # (B, E) fp32
         else:

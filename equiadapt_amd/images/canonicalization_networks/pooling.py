@@ -1,7 +1,9 @@
 """Group pooling: (B, C, G, H', W') -> (B, G) activations on the HIP streaming-reduction kernel."""
+import os
+
 import torch
 
-from equiadapt_amd import ops
+from equiadapt_amd import _lib, ops
 
 
 class _GroupPoolFn(torch.autograd.Function):
@@ -48,8 +50,6 @@ def window_sums_to_activations(S: torch.Tensor, layer, H: int, W: int) -> torch.
     weff = layer.mean_response_weights()                                # (E, Cin*k*k) fp64
     scale = 1.0 / float(O * (H - k + 1) * (W - k + 1))
     if S.is_cuda and weff.shape[0] <= 16 and not torch.is_grad_enabled():
-        from equiadapt_amd import ops
-
         return ops.window_sums_gemv(S.flatten(1), weff, scale, layer.mean_bias_value())
     act = S.flatten(1) @ weff.t() * scale
     if layer.bias is not None:
@@ -65,8 +65,6 @@ class WindowSumsLinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, S, weff, scale):
-        from equiadapt_amd import ops
-
         S, weff = S.contiguous(), weff.contiguous()
         ctx.save_for_backward(S, weff)
         ctx.scale = scale
@@ -75,11 +73,26 @@ class WindowSumsLinearFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dact):
-        from equiadapt_amd import ops
-
         S, weff = ctx.saved_tensors
         dS, dW = ops.window_sums_gemv_bwd(dact.float().contiguous(), weff, S, ctx.scale, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return dS, dW, None
+
+
+def window_grad_table(dS: torch.Tensor, H: int, W: int, k: int) -> torch.Tensor:
+    """Backward of the k*k shifted-window sums of an (H, W) map as a table: a pixel's gradient depends only on the class of its row and
+    of its column (the k-1 top / left border indices, the interior, the k-1 bottom / right ones): (B, C, k, k) -> (B, 2k-1, 2k-1, C) fp32.
+    On eqa_window_grad_table where it applies, else (and under EQA_WS_TABLE_KERNEL=0) as an fp64 mask einsum."""
+    nb, dev = k - 1, dS.device
+    if (dS.is_cuda and dS.dtype == torch.float64 and k <= ops.MAX_WINDOW_K and dS.shape[0] <= 65535 and H >= 2 * nb + 1 and W >= 2 * nb + 1
+            and os.environ.get("EQA_WS_TABLE_KERNEL", "1") != "0"):
+        return ops.window_grad_table(dS.contiguous(), H, W)       # rectangle sums from prefix sums: one launch, no library GEMM
+
+    def mask(n):
+        rep = torch.cat([torch.arange(nb), torch.tensor([nb]), torch.arange(n - nb, n)]).to(dev)       # one representative per class
+        u = torch.arange(k, device=dev)
+        return ((u[None, :] <= rep[:, None]) & (rep[:, None] <= u[None, :] + (n - k))).to(dS.dtype)    # (2nb+1, k)
+
+    return torch.einsum("tu,bcuv,sv->btsc", mask(H), dS, mask(W)).float().contiguous()
 
 
 class WindowSumsFunction(torch.autograd.Function):
@@ -90,8 +103,6 @@ class WindowSumsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, k):
-        from equiadapt_amd import ops
-
         ctx.k, ctx.shape = k, x.shape
         ctx.channels_last = x.is_contiguous(memory_format=torch.channels_last)
         return ops.window_sums(x, k)
@@ -100,34 +111,18 @@ class WindowSumsFunction(torch.autograd.Function):
     def backward(ctx, dS):
         k = ctx.k
         B, C, H, W = ctx.shape
-        nb = k - 1
-        dev = dS.device
-
-        def classes(n):
-            rep = torch.cat([torch.arange(nb), torch.tensor([nb]), torch.arange(n - nb, n)]).to(dev)       # one row per class
-            u = torch.arange(k, device=dev)
-            mask = ((u[None, :] <= rep[:, None]) & (rep[:, None] <= u[None, :] + (n - k))).to(dS.dtype)     # (2nb+1, k)
-            i = torch.arange(n, device=dev)
-            idx = torch.where(i < nb, i, torch.where(i >= n - nb, i - (n - nb) + nb + 1, torch.full_like(i, nb)))
-            return mask, idx
-
-        rm, ty = classes(H)
-        cm, tx = classes(W)
-        if dS.is_cuda and dS.dtype == torch.float64 and B <= 65535 and H >= 2 * nb + 1 and W >= 2 * nb + 1:
-            from equiadapt_amd import ops
-
-            table = ops.window_grad_table(dS.contiguous(), H, W)                     # (B, 2nb+1, 2nb+1, C), channels last
-        else:
-            table = torch.einsum("tu,bcuv,sv->btsc", rm, dS, cm).float().contiguous()
+        table = window_grad_table(dS, H, W, k)                                   # (B, 2k-1, 2k-1, C), channels last
         if table.is_cuda and C % 4 == 0:
-            from equiadapt_amd import _lib, ops
-
-            g = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
+            g = torch.empty((B, H, W, C), dtype=torch.float32, device=table.device)
+            with torch.cuda.device(table.device):
                 st = _lib.load().eqa_window_sums_bwd_expand_nhwc(table.data_ptr(), g.data_ptr(), B, H, W, C, k, ops._stream())
             _lib.check(st, "eqa_window_sums_bwd_expand_nhwc")
         else:
-            g = table[:, ty][:, :, tx]                                           # (B, H, W, C)
+            def cls(n):                                                          # class of each of n rows / columns
+                i = torch.arange(n, device=table.device)
+                return torch.where(i < k - 1, i, torch.where(i >= n - (k - 1), i - (n - (k - 1)) + k, torch.full_like(i, k - 1)))
+
+            g = table[:, cls(H)][:, :, cls(W)]                                   # (B, H, W, C)
         g = g.permute(0, 3, 1, 2)                                                # NCHW view of channels-last memory
         if not ctx.channels_last:
             g = g.contiguous()

@@ -672,6 +672,86 @@ def bn_act_bwd(gy: torch.Tensor, z: torch.Tensor, scale: torch.Tensor, shift: to
     return dz, dgamma, dbeta
 
 
+def _need_nhwc(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError(f"{name} must be a channels-last (B,C,H,W) fp32 tensor on the device")
+    return t
+
+
+def inner_bn_stats(h: torch.Tensor) -> torch.Tensor:
+    """Channels-last (B,C,H,W) -> (eqa_bn_partial_blocks, C, 2) fp64 partial sums of the per-channel sum / sum of squares (eqa_bn_stats_nhwc)."""
+    lib = _lib.load()
+    h = _need_nhwc(h, "h")
+    B, C, H, W = h.shape
+    npix = B * H * W
+    part = torch.empty((lib.eqa_bn_partial_blocks(npix), C, 2), dtype=torch.float64, device=h.device)
+    with torch.cuda.device(h.device):
+        st = lib.eqa_bn_stats_nhwc(h.data_ptr(), part.data_ptr(), npix, C, _stream())
+    _lib.check(st, "eqa_bn_stats_nhwc")
+    return part
+
+
+def inner_bn_relu_dropout(h: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, p: float, seed: int) -> torch.Tensor:
+    """y = dropout(relu(scale[c] h + shift[c]), p), channels-last (B,C,H,W); mask: a hash of (seed, element index) (eqa_bn_relu_dropout_nhwc)."""
+    lib = _lib.load()
+    h, scale, shift = _need_nhwc(h, "h"), _need(scale, "scale"), _need(shift, "shift")
+    B, C, H, W = h.shape
+    y = torch.empty_like(h)
+    with torch.cuda.device(h.device):
+        st = lib.eqa_bn_relu_dropout_nhwc(h.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), B * H * W, C, float(p), seed, _stream())
+    _lib.check(st, "eqa_bn_relu_dropout_nhwc")
+    return y
+
+
+def _inner_bn_bwd(stage: str, g, h, mean_c, rstd_c, abd, out, scale, shift, p: float, seed: int, k: int) -> torch.Tensor:
+    """One backward pass (stage: "reduce" | "apply") of dropout(relu(InnerBatchNorm(h))) into out.  k == 0: g is the channels-last
+    (B,C,H,W) upstream gradient (eqa_bn_bwd_*_nhwc; the block's output they also take is NULL: "kept and positive" is recomputed);
+    k > 0: g is the window sums' (B, 2k-1, 2k-1, C) class table (eqa_bn_bwd_*_nhwc_wsgrad)."""
+    B, C, H, W = _need_nhwc(h, "h").shape
+    if k > 0:
+        if _need(g, "table").shape != (B, 2 * k - 1, 2 * k - 1, C) or not g.is_contiguous():
+            raise ValueError(f"the class table of k = {k} on {tuple(h.shape)} is a contiguous (B, 2k-1, 2k-1, C) tensor, got {tuple(g.shape)}")
+        name, head, dims = f"eqa_bn_bwd_{stage}_nhwc_wsgrad", (g.data_ptr(),), (B, H, W, C, k)
+    else:
+        if _need_nhwc(g, "g").shape != h.shape:
+            raise ValueError(f"g {tuple(g.shape)} does not match h {tuple(h.shape)}")
+        name, head, dims = f"eqa_bn_bwd_{stage}_nhwc", (g.data_ptr(), None), (B * H * W, C)
+    vecs = [_need(v, "per-channel vector") for v in (mean_c, rstd_c, *abd, scale, shift)]
+    ptr = [v.data_ptr() for v in vecs]
+    with torch.cuda.device(h.device):
+        st = getattr(_lib.load(), name)(*head, h.data_ptr(), *ptr[:-2], float(p), out.data_ptr(), *dims, *ptr[-2:], seed, _stream())
+    _lib.check(st, name)
+    return out
+
+
+def inner_bn_bwd_reduce(g, h, mean_c, rstd_c, scale, shift, p: float, seed: int, k: int = 0) -> torch.Tensor:
+    """First backward pass of the hidden block: (eqa_bn_partial_blocks, C, 2) fp64 partial sums of the per-channel sum of the gradient
+    behind mask and ReLU and of its product with x-hat (g, k: `_inner_bn_bwd`)."""
+    B, C, H, W = h.shape
+    part = torch.empty((_lib.load().eqa_bn_partial_blocks(B * H * W), C, 2), dtype=torch.float64, device=h.device)
+    return _inner_bn_bwd("reduce", g, h, mean_c, rstd_c, (), part, scale, shift, p, seed, k)
+
+
+def inner_bn_bwd_apply(g, h, mean_c, rstd_c, a, b, d, scale, shift, p: float, seed: int, k: int = 0) -> torch.Tensor:
+    """Second backward pass: dh = a[c] (g' - b[c] - d[c] x-hat), g' the gradient behind mask and ReLU (g, k: `_inner_bn_bwd`)."""
+    return _inner_bn_bwd("apply", g, h, mean_c, rstd_c, (a, b, d), torch.empty_like(h), scale, shift, p, seed, k)
+
+
+def window_sums_nhwc_act(h: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, p: float, seed: int, k: int) -> torch.Tensor:
+    """(B,C,k,k) fp64 window sums (`window_sums`) of `inner_bn_relu_dropout`'s output without that map being written: affine map,
+    ReLU and the same dropout mask applied while the channels-last h is loaded (eqa_window_sums_nhwc_act)."""
+    lib = _lib.load()
+    h, scale, shift = _need_nhwc(h, "h"), _need(scale, "scale"), _need(shift, "shift")
+    B, C, H, W = h.shape
+    S = torch.empty((B, C, k, k), dtype=torch.float64, device=h.device)
+    ws = torch.empty((max(lib.eqa_window_sums_nhwc_workspace_bytes(B, C, H, k), 4) // 4,), dtype=torch.float32, device=h.device)
+    with torch.cuda.device(h.device):
+        st = lib.eqa_window_sums_nhwc_act(h.data_ptr(), scale.data_ptr(), shift.data_ptr(), 1, float(p), seed, S.data_ptr(), ws.data_ptr(),
+                                          B, C, H, W, k, _stream())
+    _lib.check(st, "eqa_window_sums_nhwc_act")
+    return S
+
+
 def affine_relu_rows(h: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
     """relu(h * scale[d] + shift[d]) on (rows, D) (eqa_affine_relu_rows): eval-mode BatchNorm1d + ReLU in one pass."""
     lib = _lib.load()

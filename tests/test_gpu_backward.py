@@ -829,6 +829,48 @@ def test_fused_last_block_into_window_sums_is_bit_identical(dev, group_type, N, 
         assert torch.equal(b1, b2), n1
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("training", [False, True])
+@pytest.mark.parametrize("H,W,k", [(9, 9, 5), (9, 12, 5), (5, 8, 3)])
+def test_fused_last_block_with_running_statistics_and_conv_bias(dev, H, W, k, training):
+    """InnerBnReluDropoutWindowSums on a frozen batch-norm under autograd (bn.eval(), running statistics, a convolution bias whose
+    gradient is then the per-field sum of dh) and, second case, bn.train(): against the two-stage form (InnerBnReluDropout, then
+    WindowSumsFunction) with the same dropout seed, p = 0.5 active.  Same statistics, same mask, same arithmetic per element and
+    the same summation order: S, dh, dweight, dbias, dconv_bias and the running statistics agree bit for bit.  Shapes: H x W =
+    2k-1 exactly (every row its own class), non-square, and k = 3."""
+    from equiadapt_amd.images.canonicalization_networks.escnn_networks import InnerBnReluDropout, InnerBnReluDropoutWindowSums, _InnerBatchNorm
+    from equiadapt_amd.images.canonicalization_networks.pooling import WindowSumsFunction
+
+    E, Fd, B = 4, 2, 2
+    g = torch.Generator().manual_seed(H * W + k)
+    h = (torch.randn(B, Fd * E, H, W, generator=g) * 2 + 0.5).to(dev).contiguous(memory_format=torch.channels_last)
+    up = torch.randn(B, Fd * E, k, k, dtype=torch.float64, generator=g).to(dev)
+
+    def run(fused):
+        bn = _InnerBatchNorm(Fd, momentum=0.9).to(dev)
+        with torch.no_grad():
+            bn.weight.copy_(torch.tensor([0.7, 1.4])); bn.bias.copy_(torch.tensor([-0.2, 0.3]))
+            bn.running_mean.copy_(torch.tensor([0.1, 0.6])); bn.running_var.copy_(torch.tensor([2.5, 4.0]))
+        bn.train(training)
+        h1 = h.clone().requires_grad_(True)
+        cb = torch.tensor([-0.4, 0.9], device=dev, requires_grad=True)
+        torch.manual_seed(7)                        # the dropout seed comes from torch's CPU generator
+        if fused:
+            S = InnerBnReluDropoutWindowSums.apply(h1, bn.weight, bn.bias, bn, E, cb, 0.5, True, k)
+        else:
+            S = WindowSumsFunction.apply(InnerBnReluDropout.apply(h1, bn.weight, bn.bias, bn, E, cb, 0.5, True), k)
+        (S * up).sum().backward()
+        return {"S": S.detach(), "dh": h1.grad, "dweight": bn.weight.grad, "dbias": bn.bias.grad, "dconv_bias": cb.grad,
+                "running_mean": bn.running_mean, "running_var": bn.running_var}
+
+    got, want = run(True), run(False)
+    assert (want["dconv_bias"] == 0).all().item() == training                  # batch statistics cancel the bias, running ones do not
+    for name in want:
+        print(name, (got[name].double() - want[name].double()).abs().max().item(), want[name].abs().max().item())
+    for name in want:
+        assert torch.equal(got[name], want[name]), name
+
+
 @pytest.mark.parametrize("B,HW,k,cout", [(5, (96, 96), 5, 256), (3, (68, 100), 5, 128), (4, (40, 51), 3, 64), (2, (36, 36), 5, 192)])
 def test_lift_conv_epilogue_statistics_match_the_stats_pass(dev, B, HW, k, cout):
     """eqa_lift_conv_nhwc_stats: the lifting convolution of the training step (escnn_networks.py:60-66 of the reference, feeding the

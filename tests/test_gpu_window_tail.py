@@ -19,13 +19,12 @@ def dev():
 @pytest.mark.parametrize("B,C,H,W,k", [(7, 64, 48, 48, 9), (3, 256, 88, 88, 5), (5, 24, 19, 31, 3), (2, 100, 21, 20, 10), (4, 8, 9, 9, 5), (1, 4, 5, 7, 1)])
 def test_window_grad_table_equals_the_mask_einsum(dev, B, C, H, W, k, monkeypatch):
     from equiadapt_amd import ops
-    from equiadapt_amd.images.canonicalization_networks import escnn_networks as en
-    from equiadapt_amd.images.canonicalization_networks.pooling import WindowSumsFunction
+    from equiadapt_amd.images.canonicalization_networks.pooling import WindowSumsFunction, window_grad_table as _window_grad_table
 
     dS = torch.randn(B, C, k, k, dtype=torch.float64, generator=torch.Generator().manual_seed(B * C)).to(dev)
     got = ops.window_grad_table(dS, H, W)
     monkeypatch.setenv("EQA_WS_TABLE_KERNEL", "0")
-    want = en._window_grad_table(dS, H, W, k)                       # the einsum form
+    want = _window_grad_table(dS, H, W, k)                          # the einsum form
     assert got.shape == want.shape == (B, 2 * k - 1, 2 * k - 1, C)
     assert (got - want).abs().max().item() <= 1e-5 * want.abs().max().item()
     # and through the autograd function, against autograd through an explicit unfold of the definition (fp64)

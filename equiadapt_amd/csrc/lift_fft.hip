@@ -52,16 +52,18 @@ __device__ __forceinline__ void lf_fetch_pixel(float (&p)[3], const float* __res
 __device__ __forceinline__ float lf_pixel_or_zero(float v, bool ok) { return ok ? v : 0.0f; }
 
 #ifdef EQA_LF_CLOCK
-// Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of five waves ([8 k .. 8 k + 7], k = slot:
-// waves 8, 1, 0, 6, 11), HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD), and 1 + EQA_LF_H2_DEAL of the h2
-// kernel ([63]: whether wave 6 convolves) -- tools/kbench_lift_fft.py.
-__device__ unsigned long long g_lf_clock[64];
-__device__ __forceinline__ int lf_clock_slot(int wave) { return wave == 8 ? 0 : wave == 1 ? 1 : wave == 0 ? 2 : wave == 6 ? 3 : wave == 11 ? 4 : -1; }
+// Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of six waves (slot k: waves 8, 1, 0, 6, 11, 2;
+// [8 k .. 8 k + 7] for k < 5, [64 .. 71] for k = 5; [72 + k]: the slot's row passes inside the sub-phases, FORM 2's column waves),
+// HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD), 1 + EQA_LF_H2_ROWDEAL ([62]) and 1 + EQA_LF_H2_DEAL ([63]:
+// whether wave 6 convolves) of the h2 kernel -- tools/kbench_lift_fft.py.
+__device__ unsigned long long g_lf_clock[128];
+__device__ __forceinline__ int lf_clock_slot(int wave) { return wave == 8 ? 0 : wave == 1 ? 1 : wave == 0 ? 2 : wave == 6 ? 3 : wave == 11 ? 4 : wave == 2 ? 5 : -1; }
 #define LF_CLOCK_BEGIN() const bool lfc_on = blockIdx.x == 0 && (threadIdx.x & 63) == 0 && lf_clock_slot(wave) >= 0; \
   if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) { unsigned hw_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_)); g_lf_clock[40 + wave] = hw_; } \
-  unsigned long long lfc_t = __builtin_readcyclecounter(); unsigned long long lfc_s[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define LF_CLOCK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); lfc_s[i] += n_ - lfc_t; lfc_t = n_; } while (0)
-#define LF_CLOCK_END() do { if (lfc_on) for (int i_ = 0; i_ < 8; ++i_) g_lf_clock[8 * lf_clock_slot(wave) + i_] = lfc_s[i_]; } while (0)
+  unsigned long long lfc_t = __builtin_readcyclecounter(); unsigned lfc_s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}   /* (32 bits: a launch is < 2^32 cycles) */
+#define LF_CLOCK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); lfc_s[i] += (unsigned)(n_ - lfc_t); lfc_t = n_; } while (0)
+#define LF_CLOCK_END() do { if (lfc_on) { const int k_ = lf_clock_slot(wave); \
+  for (int i_ = 0; i_ < 8; ++i_) g_lf_clock[(k_ < 5 ? 8 * k_ : 64) + i_] = lfc_s[i_]; g_lf_clock[72 + k_] = lfc_s[8]; } } while (0)
 #else
 #define LF_CLOCK_BEGIN() do { } while (0)
 #define LF_CLOCK(i) do { } while (0)
@@ -125,8 +127,12 @@ __device__ __forceinline__ LfItem lf_item(unsigned work, int ngrp, int TY, int T
 // FORM 2 deals them differently: waves 0..5 kCols; waves 6..11 kConv AND the patch staging, six of a sub-phase's 36 tiles each (half a
 // tile column).  Waves w, w + 4, w + 8 of a block share a SIMD (HW_REG_HW_ID, profiles/r07/wave_simd.txt): SIMDs 2 and 3 carry TWO
 // convolution waves (6 | 10, 7 | 11), which cover each other's window reads and epilogues on the matrix pipe (48 tiles per item in 17 k
-// cycles, where a wave alone takes 15 k for 24: profiles/r14); waves 8 and 9 are alone on theirs.  No row pass beside the convolution:
-// all twelve run in the tail, one per wave (lf_h2_run: who convolves what; lf_h2_rows: who transforms which rows).
+// cycles, where a wave alone takes 15 k for 24: profiles/r14); waves 8 and 9 are alone on theirs and wait for those two at every
+// sub-phase's second barrier.  No convolution wave transforms rows.  The column waves do, and six of the twelve passes (four rows
+// each) DURING the convolution: in each of sub-phases 1..3, behind their stores of that sub-phase, waves 1 and 4 -- one on each of the
+// lone convolution waves' SIMDs -- transform two passes of rows that an earlier sub-phase finished, while they still hold what is
+// left of the previous item's spectrum; the tail keeps six passes, one per column wave (lf_h2_run: who convolves what;
+// lf_h2_rowmask: who transforms which rows when; profiles/r17).
 // EQA_LF_H2_DEAL = 0 is the dealing of profiles/r07 .. r13: waves 8..11 kConv, one per SIMD, nine tiles each; waves 6 and 7 kRowp.
 enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2, EQA_LF_H2_DEAL = 0 only): waves 6, 7 -- staging and row transforms, no convolution
 
@@ -143,7 +149,7 @@ enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2, EQA_LF_H2_DEAL = 0
 // sub-phase's first), the static_assert below that every tile is taken exactly once.
 //   EQA_LF_H2_DEAL = 1  SIX convolution waves 6..11, half a tile column (six tiles) each, no run crosses a column.  Waves 6 | 10 and
 //                       7 | 11 share a SIMD and cover each other's window reads and epilogues; 8 and 9 are alone on theirs.  No row
-//                       pass beside the convolution: all twelve wait for the tail, one per wave (the fp32 form's tail).
+//                       pass on a convolution wave's own stream: EQA_LF_H2_ROWDEAL (below) deals them to the column waves and the tail.
 //   EQA_LF_H2_DEAL = 0  FOUR convolution waves 8..11, one per SIMD, nine tiles each in column-major order (tile n: column n / 12, row
 //                       n % 12): wave 8 column 0 rows 0..8, wave 11 column 2 rows 3..11; waves 9 and 10 three rows at the end / start of a
 //                       column, then six of the middle column.  Waves 6, 7: kRowp (profiles/r07 .. r13).
@@ -153,7 +159,6 @@ enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2, EQA_LF_H2_DEAL = 0
 constexpr int kLhDeal = EQA_LF_H2_DEAL;
 constexpr int kLhRun0 = kLhDeal == 0 ? 3 : 6, kLhRun1 = kLhDeal == 0 ? 6 : 0;
 constexpr int kLhFirstConv = kLhDeal == 0 ? 8 : 6;     // waves kLhFirstConv..11: kConv; waves 6 .. kLhFirstConv - 1: kRowp
-constexpr bool kLhConvRowsInTail = kLhDeal != 0;       // the convolution waves take a row pass of the tail
 struct LfRun { int y0, t0, y1, t1; bool cross; };      // rows y0 .. y0 + kLhRun0 - 1 of column t0, then y1 .. y1 + kLhRun1 - 1 of column t1
 __host__ __device__ constexpr LfRun lf_h2_run(int wave, int /*sub: every sub-phase is dealt alike*/) {
   if (kLhDeal == 0) {
@@ -185,8 +190,63 @@ constexpr bool lf_h2_deal_covers() {
 }
 static_assert(lf_h2_deal_covers(), "FORM 2: a tile of the sub-phase is left to no wave or taken by two");
 
-#if EQA_LF_H2_DEAL != 0        // every row pass in the tail: wave w rows 4 w .. 4 w + 3
-__device__ __forceinline__ int lf_h2_rows(int wave, int s) { return s < 4 ? 0 : 4 * wave; }
+#if EQA_LF_H2_DEAL != 0
+// FORM 2's row dealing (EQA_LF_H2_DEAL != 0).  Pass k = tile rows 4 k .. 4 k + 3, k = 0..11; sub-phase s convolves passes 3 s .. 3 s + 2;
+// WINDOW s = the stretch of sub-phase s between its two barriers.  Pass k is complete when sub-phase k / 3 has passed its second
+// barrier, so it may run in any window s > k / 3 or in the tail (s = 4), on a wave that has nothing else to issue there: a column
+// wave, whose stores of the window are out and drain while it transforms.  lf_h2_rowmask: bit k = the wave runs pass k in window s
+// (at most one per wave and window: a pass is ~100 registers and the code of one call); the static_assert below walks the table.
+//   EQA_LF_H2_ROWDEAL = 3  in each of windows 1, 2, 3 TWO passes, on column waves 1 and 4: one on each of the two SIMDs whose convolution
+//                          wave (9, 8) is alone and waits for the shared SIMDs at the second barrier anyway -- window s passes
+//                          2 (s - 1) and 2 (s - 1) + 1.  The tail keeps passes 6..11 on the six column waves (two per SIMD at most:
+//                          3.4 k cycles where three per SIMD took 6.1 k).  No convolution wave carries a pass.  Three passes per
+//                          window, i.e. two on one of those SIMDs, cost the convolution what the tail gained (profiles/r17).
+//   EQA_LF_H2_ROWDEAL = 0  all twelve in the tail, wave w pass w (profiles/r14)
+#ifndef EQA_LF_H2_ROWDEAL
+#define EQA_LF_H2_ROWDEAL 3
+#endif
+constexpr int kLhRowDeal = EQA_LF_H2_ROWDEAL;
+static_assert(kLhRowDeal == 0 || kLhRowDeal == 3, "EQA_LF_H2_ROWDEAL: 0 or 3 (1 and 2 were measured and removed: profiles/r17)");
+__host__ __device__ constexpr int lf_h2_rowmask(int wave, int s) {
+  if (kLhRowDeal == 0) return s < 4 ? 0 : 1 << wave;
+  if (s < 4) return s < 1 ? 0 : wave == 1 ? 1 << (2 * (s - 1)) : wave == 4 ? 1 << (2 * (s - 1) + 1) : 0;
+  return wave < 6 ? 1 << (6 + wave) : 0;
+}
+constexpr bool lf_h2_rowdeal_covers() {
+  int n[12] = {};
+  for (int s = 0; s <= 4; ++s)
+    for (int w = 0; w < 12; ++w) {
+      const int m = lf_h2_rowmask(w, s);
+      if (m & ~0xfff) return false;
+      if (s < 4 && w >= 6 && m) return false;        // inside a sub-phase only the column waves have a slot for a pass
+      if (m & (m - 1)) return false;                 // one pass per wave and window
+      for (int k = 0; k < 12; ++k)
+        if (m & (1 << k)) {
+          if (s <= k / 3) return false;              // in front of the barrier its rows' convolution sits behind
+          ++n[k];
+        }
+    }
+  for (int k = 0; k < 12; ++k)
+    if (n[k] != 1) return false;
+  return true;
+}
+static_assert(lf_h2_rowdeal_covers(), "FORM 2: a row pass is run by no wave or by two, or in a window in which its rows are not convolved yet");
+constexpr bool lf_h2_window_has_pass(int s) {
+  for (int w = 0; w < 6; ++w)
+    if (lf_h2_rowmask(w, s)) return true;
+  return false;
+}
+constexpr bool lf_h2_conv_rows_in_tail() {
+  for (int w = 6; w < 12; ++w)
+    if (lf_h2_rowmask(w, 4)) return true;
+  return false;
+}
+// the first row of the wave's pass of window s = 1..3 or of the tail (s = 4), or -1
+__device__ __forceinline__ int lf_h2_rows(int wave, int s) {
+  if (kLhRowDeal == 0 && s == 4) return 4 * wave;      // (the table's answer, in the instructions of profiles/r14)
+  const int m = lf_h2_rowmask(wave, s);
+  return m ? 4 * __builtin_ctz(m) : -1;
+}
 #elif defined(EQA_LF_H2_ROWS_IN_SUB)   // variant: the third pass alternates between waves 6 and 7, the tail keeps rows 36..47 (1.08 ms, not 1.02)
 __device__ __forceinline__ int lf_h2_rows(int wave, int s) {
   if (s < 4) return wave == 6 ? (1 | ((s & 1) ? 4 : 0)) : (wave == 7 ? (2 | ((s & 1) ? 0 : 4)) : 0);
@@ -197,6 +257,10 @@ __device__ __forceinline__ int lf_h2_rows(int wave, int s) {
   if (s < 4) return wave == 6 ? 1 : (wave == 7 ? 2 : 0);
   return wave == 6 ? 36 : wave == 7 ? 40 : wave == 0 ? 8 : wave == 4 ? 20 : wave == 1 ? 32 : wave == 5 ? 44 : -1;
 }
+#endif
+#if EQA_LF_H2_DEAL == 0        // (the passes inside the sub-phases are those of waves 6, 7: kRowp)
+constexpr bool lf_h2_window_has_pass(int) { return false; }
+constexpr bool lf_h2_conv_rows_in_tail() { return false; }
 #endif
 
 template <class F, int... Is>
@@ -925,6 +989,16 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
         LF_CLOCK(1);
         col_work(SUB);
         LF_CLOCK(2);
+        if constexpr (H2) {
+          // the wave's row pass of this window (lf_h2_rowmask: rows of an EARLIER sub-phase of the item being convolved), behind
+          // the window's stores in program order: they drain while it computes.  Of the pending item's spectrum 96 - 24 (sub + 1)
+          // registers are still waiting for their stores beside it.
+          if constexpr (sub > 0 && lf_h2_window_has_pass(sub)) {
+            const int a = lf_h2_rows(wave, sub);
+            if (live && a >= 0) row_pass(a);
+            LF_CLOCK(8);
+          }
+        }
         __syncthreads();
         LF_CLOCK(3);
         if constexpr (PIECES) {
@@ -943,8 +1017,8 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
     if constexpr (PIECES) {
       if (live) row_pass(4 * wave);
     } else if constexpr (H2) {
-      // (a convolution wave's pass runs behind its last run: of the convolution only wh and bias4 are live beside it)
-      if constexpr (ROLE != kConv || kLhConvRowsInTail) {
+      // (a convolution wave's pass -- EQA_LF_H2_ROWDEAL = 0 -- runs behind its last run: of the convolution only wh and bias4 are live beside it)
+      if constexpr (ROLE != kConv || lf_h2_conv_rows_in_tail()) {
         const int a = lf_h2_rows(wave, NSUB);
         if (live && a >= 0) row_pass(a);
       }
@@ -1030,7 +1104,12 @@ __global__ __launch_bounds__(kLfThreads) void lift5_fft48_fused_h2_kernel(const 
   else if (w >= kLhFirstConv) lift5_fft48_body<kConv, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
   else if constexpr (kLhFirstConv > 6) lift5_fft48_body<kRowp, 2>(x, bank, bias, relu, V, H0, W0, C, TY, TX, Mp, nwork, v_bytes, x_bytes, bank_bytes, dcmax, xbound, nxbound, w_scale);
 #ifdef EQA_LF_CLOCK
-  if (blockIdx.x == 0 && threadIdx.x == 0) g_lf_clock[63] = 1 + kLhDeal;    // tools/kbench_lift_fft.py: what wave 6 does
+  if (blockIdx.x == 0 && threadIdx.x == 0) {     // tools/kbench_lift_fft.py: what wave 6 does, where the row passes run
+    g_lf_clock[63] = 1 + kLhDeal;
+#if EQA_LF_H2_DEAL != 0
+    g_lf_clock[62] = 1 + kLhRowDeal;
+#endif
+  }
 #endif
 }
 

@@ -78,9 +78,9 @@ def main():
         print(f"{name:>56}: {e0.elapsed_time(e1) / a.reps:7.3f} ms per launch  (B = {B}, {C} channels, {S} x {S})")
     raw = ctypes.CDLL(_lib.SO_PATH)
     if hasattr(raw, "eqa_debug_lf_clock"):
-        # a clock build: [8 k .. 8 k + 7] the phases of the wave in slot k (older builds: the first three slots only), [40 + w] the
-        # HW_REG_HW_ID of wave w of block 0 (older builds: 0)
-        out = (ctypes.c_ulonglong * 64)()
+        # a clock build: [8 k .. 8 k + 7] the phases of the wave in slot k < 5, [64 .. 71] those of slot 5 (older builds: fewer slots),
+        # [72 + k] the slot's row passes inside the sub-phases (older builds: 0), [40 + w] the HW_REG_HW_ID of wave w of block 0
+        out = (ctypes.c_ulonglong * 128)()
         form = os.environ.get("EQA_LIFT_FFT_FORM", "h2")
         (fused_p if form == "bf16x3" else fused_h if form == "h2" else fused)()
         torch.cuda.synchronize()
@@ -89,15 +89,20 @@ def main():
         items = max(1, (M * (C // 16) + 255) // 256) if M * (C // 16) >= 256 else 1
         hw = [out[40 + w] for w in range(12)]
         simd = {w: (hw[w] >> 4) & 3 for w in range(12)} if any(hw) else {}
-        # [63]: 1 + EQA_LF_H2_DEAL of the h2 kernel (older builds: 0) -- from dealing 1 on wave 6 convolves
+        # [63]: 1 + EQA_LF_H2_DEAL of the h2 kernel (older builds: 0) -- from dealing 1 on wave 6 convolves; [62]: 1 + EQA_LF_H2_ROWDEAL
+        # (older builds: 0) -- from row dealing 1 on column waves transform rows inside the sub-phases
         wave6 = "convolution wave 6" if form == "h2" and out[63] >= 2 else "row-transform wave 6"
-        for base, w, who in ((0, 8, "convolution wave 8"), (8, 1, "column wave 1"), (16, 0, "column wave 0 (packed)"),
-                             (24, 6, wave6), (32, 11, "convolution wave 11")):
-            tot = sum(out[base:base + 8])
+        if form == "h2" and out[62]:
+            print(f"EQA_LF_H2_DEAL = {out[63] - 1}, EQA_LF_H2_ROWDEAL = {out[62] - 1}")
+        for k, (base, w, who) in enumerate(((0, 8, "convolution wave 8"), (8, 1, "column wave 1"), (16, 0, "column wave 0 (packed)"),
+                                            (24, 6, wave6), (32, 11, "convolution wave 11"), (64, 2, "column wave 2"))):
+            tot = sum(out[base:base + 8]) + out[72 + k]
             if tot == 0:
                 continue
             at = f" [SIMD {simd[w]}]" if simd else ""
-            print(f"{who}{at}: cycles per item (block 0, {items} items): " + " | ".join(f"{n}: {out[base + i] // items}" for i, n in enumerate(names)) + f" | total {tot // items}")
+            rows = f" | row passes in the sub-phases: {out[72 + k] // items}" if form == "h2" and w < 6 and out[62] else ""
+            print(f"{who}{at}: cycles per item (block 0, {items} items): " + " | ".join(f"{n}: {out[base + i] // items}" for i, n in enumerate(names))
+                  + rows + f" | total {tot // items}")
         if simd:
             print("block 0, HW_REG_HW_ID per wave: " + " ".join(f"w{w}:0x{hw[w]:x}(simd {simd[w]}, wave slot {hw[w] & 15}, cu {(hw[w] >> 8) & 15})" for w in range(12)))
 

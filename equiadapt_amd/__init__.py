@@ -65,9 +65,14 @@ from equiadapt_amd.pointcloud.canonicalization.continuous_group import (  # noqa
 )
 from equiadapt_amd.pointcloud.canonicalization_networks import (  # noqa: F401
     VNBatchNorm,
+    VNBilinear,
+    VNLeakyReLU,
+    VNLinear,
     VNLinearLeakyReLU,
     VNMaxPool,
     VNSmall,
+    VNSoftplus,
+    VNStdFeature,
     equivariant_networks,
     get_graph_feature_cross,
 )
@@ -87,6 +92,8 @@ __all__ = [
     "get_action_on_image_features", "get_graph_feature_cross", "gram_schmidt",
     # not in the reference's __all__, part of this package's surface
     "EuclideanGroupNBody", "VNDeepSets", "flip_boxes", "flip_masks", "roll_by_gather", "rotate_boxes", "rotate_masks", "rotate_points",
+    # the rest of the reference's vector_neuron_layers.py (in the reference's __all__)
+    "VNBilinear", "VNLeakyReLU", "VNLinear", "VNSoftplus", "VNStdFeature",
 ]
 
 __version__ = "0.1.0"

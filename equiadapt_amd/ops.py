@@ -1232,3 +1232,47 @@ def vndeepsets_bwd(loc, vel, charges, adj, packed, mask, saved, grad_rot, grad_t
                                     int(final_mean), int(canon_translation), _stream())
     _lib.check(st, "eqa_vndeepsets_bwd")
     return partial
+
+
+def _vn_act_args(x: torch.Tensor, Wd: torch.Tensor, what: str):
+    x = _need(x, "x")
+    Wd = _need(Wd, "Wd")
+    if x.dim() < 3 or x.shape[2] != 3 or x.numel() == 0:
+        raise ValueError(f"{what} expects a non-empty (B, C, 3, ...) tensor, got {tuple(x.shape)}")
+    B, C = x.shape[0], x.shape[1]
+    if Wd.dim() != 2 or Wd.shape[1] != C or Wd.shape[0] not in (1, C):
+        raise ValueError(f"{what}: Wd must be ({C}, {C}) or (1, {C}), got {tuple(Wd.shape)}")
+    return x, Wd, B, C, x.numel() // (B * C * 3), Wd.shape[0]
+
+
+def vn_act_max_channels() -> int:
+    """The widest layer the fused vector-neuron activation takes (eqa_vn_act_max_channels)."""
+    return _lib.load().eqa_vn_act_max_channels()
+
+
+def vn_act(x: torch.Tensor, Wd: torch.Tensor, softplus: bool, slope: float) -> torch.Tensor:
+    """VNLeakyReLU (softplus False) or VNSoftplus of x:(B, C, 3, ...) with the direction map Wd:(C or 1, C), one pass
+    (eqa_vn_act_fwd).  No autograd."""
+    lib = _lib.load()
+    x, Wd, B, C, P, D = _vn_act_args(x, Wd, "vn_act")
+    y = torch.empty_like(x)
+    with torch.cuda.device(x.device), _timed("vn_act"):
+        st = lib.eqa_vn_act_fwd(x.data_ptr(), Wd.data_ptr(), y.data_ptr(), B, C, P, D, int(softplus), slope, _stream())
+    _lib.check(st, "eqa_vn_act_fwd")
+    return y
+
+
+def vn_act_backward(x: torch.Tensor, Wd: torch.Tensor, gy: torch.Tensor, softplus: bool, slope: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dL/dx, dL/dWd) of `vn_act` for gy = dL/dy (eqa_vn_act_bwd); the per-block sums of dL/dWd are added here, in a fixed order."""
+    lib = _lib.load()
+    x, Wd, B, C, P, D = _vn_act_args(x, Wd, "vn_act_backward")
+    gy = _need(gy, "gy")
+    if gy.shape != x.shape:
+        raise ValueError(f"gy must be shaped like x {tuple(x.shape)}, got {tuple(gy.shape)}")
+    gx = torch.empty_like(x)
+    partial = torch.empty(lib.eqa_vn_act_bwd_blocks(B * P), D, C, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("vn_act_bwd"):
+        st = lib.eqa_vn_act_bwd(x.data_ptr(), Wd.data_ptr(), gy.data_ptr(), gx.data_ptr(), partial.data_ptr(), B, C, P, D,
+                                int(softplus), slope, _stream())
+    _lib.check(st, "eqa_vn_act_bwd")
+    return gx, partial.sum(0)

@@ -5,8 +5,13 @@ from equiadapt_amd.pointcloud.canonicalization_networks.equivariant_networks imp
 )
 from equiadapt_amd.pointcloud.canonicalization_networks.vector_neuron_layers import (  # noqa: F401
     VNBatchNorm,
+    VNBilinear,
+    VNLeakyReLU,
+    VNLinear,
     VNLinearLeakyReLU,
     VNMaxPool,
+    VNSoftplus,
+    VNStdFeature,
     mean_pool,
 )
 from equiadapt_amd.pointcloud.canonicalization_networks import equivariant_networks  # noqa: E402,F401

@@ -843,6 +843,27 @@ int eqa_vndeepsets_bwd(const float* loc, const float* vel, const float* charges,
                        int H, int L, int features, int softplus, float slope, int layer_mean, int final_mean, int canon_translation,
                        void* stream);
 
+/*
+ * The directional nonlinearity of the vector-neuron layers, stand-alone (VNSoftplus and VNLeakyReLU of
+ * equiadapt/pointcloud/canonicalization_networks/vector_neuron_layers.py:93-151 and :154-207).  x, y, gy, gx: (B, C, 3, P) fp32,
+ * contiguous, P = the product of the trailing axes (1 for a (B, C, 3) input); Wd:(D, C), D = C, or 1 for share_nonlinearity.
+ * Per point and channel, with d_o = sum_i Wd[o,i] x_i (o = 0 for every channel when D = 1) and t = <x,d> / (|d|^2 + 1e-6):
+ *   y = slope x + (1 - slope) (mask x + (1 - mask) (x - t d)),   softplus = 0: mask = [<x,d> >= 0],
+ *   softplus = 1: mask = (1 + c) / 2, c = <x,d> / (|x||d| + 1e-6) -- the closed form of the reference's cos^2(acos(c) / 2); its
+ *   gradient stays finite where d is parallel to x, where the reference's gradient through acos is not.
+ *   eqa_vn_act_max_channels  the largest C the kernels take (96: the backward's LDS); more: EQA_ERR_UNSUPPORTED
+ *   eqa_vn_act_fwd           y from x, one read and one write
+ *   eqa_vn_act_bwd           gx and partial:(eqa_vn_act_bwd_blocks(B * P), D, C), whose sum over rows is dL/dWd; d and the gate are
+ *                            recomputed from x
+ * NULL pointers, D not in {1, C}, non-positive sizes: EQA_ERR_INVALID_ARG.  Plain loads and stores only, per-block sums in a fixed
+ * order: two launches on the same input give the same bits.  Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_vn_act_max_channels(void);
+int eqa_vn_act_bwd_blocks(long long points);
+int eqa_vn_act_fwd(const float* x, const float* Wd, float* y, int B, int C, long long P, int D, int softplus, float slope, void* stream);
+int eqa_vn_act_bwd(const float* x, const float* Wd, const float* gy, float* gx, float* partial, int B, int C, long long P, int D,
+                   int softplus, float slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

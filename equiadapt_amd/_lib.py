@@ -175,6 +175,9 @@ SIGNATURES = {
     "eqa_gram_schmidt_bwd": (_int, [_vp, _vp, _vp, _int, _vp]),
     "eqa_modified_gram_schmidt": (_int, [_vp, _vp, _int, _vp]),
     "eqa_rigid_rows": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "eqa_nbody_frame_fwd": (_int, [_vp] * 7 + [_int, _vp]),
+    "eqa_nbody_frame_bwd": (_int, [_vp] * 12 + [_int, _vp]),
+    "eqa_rigid_rows_bwd": (_int, [_vp] * 5 + [_int, _vp]),
     "eqa_fourier_elu_fwd": (_int, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _int, _vp]),
     "eqa_fourier_elu_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _int, _vp]),
     "eqa_vndeepsets_param_count": (_int, [_int] * 3),

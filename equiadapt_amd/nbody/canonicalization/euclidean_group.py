@@ -4,31 +4,122 @@ Reference: equiadapt/nbody/canonicalization/euclidean_group.py:8-157.  Same API:
 keyword arguments ``loc, edges, vel, edge_attr, charges`` in that order, ``canonicalize`` returning
 ``(canonical_loc, canonical_vel)``, ``invert_canonicalization`` mapping predicted locations back (``x R + t``).
 The canonicalization network is ``equiadapt_amd.nbody.VNDeepSets`` (the reference's network of that name, one launch on the
-device) or any module returning ``(rotation_vectors (M,3,3), translation_vectors (M,3))``; the rigid actions and the modified Gram-Schmidt run as HIP kernels
-(forward only -- n-body training keeps the op-by-op path, selected automatically when autograd is recording).
+device) or any module returning ``(rotation_vectors (M,3,3), translation_vectors (M,3))``.
+
+Behind the network the modified Gram-Schmidt and the rigid actions run as HIP kernels, in inference and in training:
+
+* ``canonicalize`` is one launch, ``eqa_nbody_frame_fwd`` (frame, canonical locations, canonical velocities); under autograd its
+  backward is one launch as well, ``eqa_nbody_frame_bwd``.  Taken when neither ``get_groupelement`` nor ``modified_gram_schmidt``
+  is overridden in a subclass; a subclass that overrides one keeps its own steps, each on its own kernel.
+* ``modified_gram_schmidt`` on its own is ``eqa_modified_gram_schmidt``; under autograd its backward is ``eqa_nbody_frame_bwd`` with
+  the two action gradients absent.
+* ``invert_canonicalization`` is ``eqa_rigid_rows``; under autograd its backward is ``eqa_rigid_rows_bwd``.
+
+Route rule: fp32 device tensors on one device, shaped (M,3,3) / (M,3) with M >= 1 (made contiguous first); the train route when
+autograd is recording and one of them requires grad, the inference route otherwise.  Anything else -- fp64, CPU tensors,
+``EQA_NBODY_FRAME_KERNEL=0`` -- takes the reference's op-by-op path.  ``last_route`` (canonicalize, or a lone
+``modified_gram_schmidt``) and ``last_invert_route`` say which one ran: "fused-inference", "fused-train" or "plain: <why>".
+The Functions are once-differentiable: no double backward.
 """
+import os
 from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from equiadapt_amd import ops
 from equiadapt_amd.common.basecanonicalization import ContinuousGroupCanonicalization
+
+_FRAME_KERNEL = "EQA_NBODY_FRAME_KERNEL"      # "0": the op-by-op path on the device as well (A/B timing: tools/kbench_nbody.py)
+
+
+def _frame_route(mats: Tuple[torch.Tensor, ...], rows: Tuple[torch.Tensor, ...]) -> str:
+    """"fused-train", "fused-inference" or "plain: <why>" for (M,3,3) tensors ``mats`` and (M,3) tensors ``rows``."""
+    if os.environ.get(_FRAME_KERNEL, "1") == "0":
+        return f"plain: {_FRAME_KERNEL}=0"
+    tensors = mats + rows
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return "plain: inputs are not fp32 device tensors"
+    if any(t.device != tensors[0].device for t in tensors):
+        return "plain: inputs are on different devices"
+    M = tensors[0].shape[0] if tensors[0].dim() else 0
+    if M < 1 or any(tuple(t.shape) != (M, 3, 3) for t in mats) or any(tuple(t.shape) != (M, 3) for t in rows):
+        return "plain: shapes are not (M,3,3) / (M,3) with M >= 1"
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return "fused-train"
+    return "fused-inference"
+
+
+class _NBodyFrameFn(torch.autograd.Function):
+    """(v, t, loc, vel) -> (R, cloc, cvel): eqa_nbody_frame_fwd / eqa_nbody_frame_bwd, one launch each."""
+
+    @staticmethod
+    def forward(ctx, v, t, loc, vel):
+        v, t, loc, vel = v.contiguous(), t.contiguous(), loc.contiguous(), vel.contiguous()
+        R, cloc, cvel = ops.nbody_frame_fwd(v, t, loc, vel)
+        ctx.save_for_backward(v, t, loc, vel, R)
+        ctx.set_materialize_grads(False)                 # an output the loss does not reach arrives as None: NULL for the kernel
+        return R, cloc, cvel
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gR, gcloc, gcvel):
+        v, t, loc, vel, R = ctx.saved_tensors
+        if gR is None and gcloc is None and gcvel is None:
+            return None, None, None, None
+        return ops.nbody_frame_bwd(v, t, loc, vel, R, gR, gcloc, gcvel, need=tuple(ctx.needs_input_grad))
+
+
+class _ModifiedGramSchmidtFn(torch.autograd.Function):
+    """v -> R: eqa_modified_gram_schmidt; backward eqa_nbody_frame_bwd without the action gradients."""
+
+    @staticmethod
+    def forward(ctx, v):
+        v = v.contiguous()
+        ctx.save_for_backward(v)
+        return ops.modified_gram_schmidt(v)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gR):
+        (v,) = ctx.saved_tensors
+        return ops.nbody_frame_bwd(v, None, None, None, None, gR, None, None, need=(True, False, False, False))[0]
+
+
+class _RigidRowsFn(torch.autograd.Function):
+    """(x, R, t) -> x R + t: eqa_rigid_rows mode 0 / eqa_rigid_rows_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, R, t):
+        x, R = x.contiguous(), R.contiguous()
+        ctx.save_for_backward(x, R)
+        return ops.rigid_rows(x, R, t, inverse=False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, R = ctx.saved_tensors
+        need_x, need_R, need_t = ctx.needs_input_grad
+        gx = gR = None
+        if need_x or need_R:
+            gx, gR = ops.rigid_rows_bwd(x, R, g, need=(need_x, need_R))
+        return gx, gR, (g if need_t else None)
 
 
 class EuclideanGroupNBody(ContinuousGroupCanonicalization):
     def __init__(self, canonicalization_network: torch.nn.Module) -> None:
         super().__init__(canonicalization_network)
+        self.last_route: Optional[str] = None            # "fused-inference" | "fused-train" | "plain: <why>"
+        self.last_invert_route: Optional[str] = None
 
     def forward(self, x: torch.Tensor, targets: Optional[List] = None, **kwargs: Any):
         return self.canonicalize(x, None, **kwargs)
 
-    @staticmethod
-    def _fused(*tensors: torch.Tensor) -> bool:
-        return all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and not (
-            torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
-
     def modified_gram_schmidt(self, vectors: torch.Tensor) -> torch.Tensor:
-        if self._fused(vectors):
+        self.last_route = route = _frame_route((vectors,), ())
+        if route == "fused-train":
+            return _ModifiedGramSchmidtFn.apply(vectors)
+        if route == "fused-inference":
             return ops.modified_gram_schmidt(vectors)
         v1 = vectors[:, 0] / torch.norm(vectors[:, 0], dim=1, keepdim=True)
         v2 = vectors[:, 1] - torch.sum(vectors[:, 1] * v1, dim=1, keepdim=True) * v1
@@ -38,9 +129,7 @@ class EuclideanGroupNBody(ContinuousGroupCanonicalization):
         v3 = v3 / torch.norm(v3, dim=1, keepdim=True)
         return torch.stack([v1, v2, v3], dim=1)
 
-    def get_groupelement(self, nodes, loc, edges, vel, edge_attr, charges) -> Dict[str, torch.Tensor]:
-        rotation_vectors, translation_vectors = self.canonicalization_network(nodes, loc, edges, vel, edge_attr, charges)
-        rotation_matrix = self.modified_gram_schmidt(rotation_vectors)
+    def _set_groupelement(self, rotation_matrix: torch.Tensor, translation_vectors: torch.Tensor) -> Dict[str, torch.Tensor]:
         if not hasattr(self, "canonicalization_info_dict"):
             self.canonicalization_info_dict = {}
         element = {"rotation_matrix": rotation_matrix, "translation_vectors": translation_vectors,
@@ -48,13 +137,38 @@ class EuclideanGroupNBody(ContinuousGroupCanonicalization):
         self.canonicalization_info_dict["group_element"] = element
         return element
 
+    def get_groupelement(self, nodes, loc, edges, vel, edge_attr, charges) -> Dict[str, torch.Tensor]:
+        rotation_vectors, translation_vectors = self.canonicalization_network(nodes, loc, edges, vel, edge_attr, charges)
+        return self._set_groupelement(self.modified_gram_schmidt(rotation_vectors), translation_vectors)
+
+    def _own_frame_steps(self) -> bool:
+        cls = type(self)
+        return (cls.get_groupelement is EuclideanGroupNBody.get_groupelement
+                and cls.modified_gram_schmidt is EuclideanGroupNBody.modified_gram_schmidt)
+
     def canonicalize(self, x: torch.Tensor, targets: Optional[List] = None, **kwargs: Any
                      ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
         self.device = x.device
         loc, edges, vel, edge_attr, charges = kwargs.values()
-        el = self.get_groupelement(x, loc, edges, vel, edge_attr, charges)
+        if self._own_frame_steps():
+            # the network, then frame and both actions in one launch (and one more for the backward)
+            v, t = self.canonicalization_network(x, loc, edges, vel, edge_attr, charges)
+            route = _frame_route((v,), (t, loc, vel))
+            if not route.startswith("plain"):
+                self.last_route = route
+                if route == "fused-train":
+                    R, canonical_loc, canonical_vel = _NBodyFrameFn.apply(v, t, loc, vel)
+                else:
+                    R, canonical_loc, canonical_vel = ops.nbody_frame_fwd(v, t, loc, vel)
+                self._set_groupelement(R, t)
+                return canonical_loc, canonical_vel
+            el = self._set_groupelement(self.modified_gram_schmidt(v), t)
+            self.last_route = route
+        else:
+            el = self.get_groupelement(x, loc, edges, vel, edge_attr, charges)
+            self.last_route = "plain: get_groupelement or modified_gram_schmidt is overridden"
         R, t = el["rotation_matrix"], el["translation_vectors"]
-        if self._fused(loc, vel, R, t):
+        if _frame_route((R,), (t, loc, vel)) == "fused-inference":
             return ops.rigid_rows(loc, R, t, inverse=True), ops.rigid_rows(vel, R, None, inverse=True)
         Rinv = el["rotation_matrix_inverse"]
         canonical_loc = torch.bmm(loc[:, None, :], Rinv).squeeze() - torch.bmm(t[:, None, :], Rinv).squeeze()
@@ -62,6 +176,9 @@ class EuclideanGroupNBody(ContinuousGroupCanonicalization):
 
     def invert_canonicalization(self, x_canonicalized_out: torch.Tensor, **kwargs: Any) -> torch.Tensor:
         R, t, _ = self.canonicalization_info_dict["group_element"].values()
-        if self._fused(x_canonicalized_out, R, t):
+        self.last_invert_route = route = _frame_route((R,), (x_canonicalized_out, t))
+        if route == "fused-train":
+            return _RigidRowsFn.apply(x_canonicalized_out, R, t)
+        if route == "fused-inference":
             return ops.rigid_rows(x_canonicalized_out, R, t, inverse=False)
         return torch.bmm(x_canonicalized_out[:, None, :], R).squeeze() + t

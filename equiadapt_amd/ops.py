@@ -1078,7 +1078,102 @@ def rigid_rows(x: torch.Tensor, R: torch.Tensor, t: Optional[torch.Tensor], inve
     return out
 
 
-FOURIER_FIELD_DIM = 9   # channels of a band-limited SO(2) field: a_0, (Re, Im) c_1..c_4 (csrc/fourier_act.hip)
+def _rows(what: str, M: Optional[int], **named) -> int:
+    """Every given tensor is (M, *tail): named as name=(tensor or None, tail); returns M.  Shapes are judged before anything else, so
+    a wrong one is a ValueError whatever device it is on."""
+    for name, (t, tail) in named.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or (M is not None and t.shape[0] != M):
+            want = ",".join(str(d) for d in ("M" if M is None else M,) + tail)
+            raise ValueError(f"{what}: {name} must be ({want}), got {tuple(t.shape)}")
+        M = t.shape[0]
+    return M
+
+
+def nbody_frame_fwd(v: torch.Tensor, t: torch.Tensor, loc: torch.Tensor, vel: torch.Tensor
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The n-body canonicalizer's forward in one launch: v:(M,3,3), t, loc, vel:(M,3) -> (R, cloc, cvel), the bits of
+    `modified_gram_schmidt` followed by `rigid_rows(loc, R, t, inverse=True)` and `rigid_rows(vel, R, None, inverse=True)`
+    (eqa_nbody_frame_fwd)."""
+    for name, x in (("vectors", v), ("t", t), ("loc", loc), ("vel", vel)):
+        if x is None:
+            raise TypeError(f"{name} must be a torch.Tensor")
+    M = _rows("nbody_frame_fwd", None, vectors=(v, (3, 3)), t=(t, (3,)), loc=(loc, (3,)), vel=(vel, (3,)))
+    lib = _lib.load()
+    v, t, loc, vel = _need(v, "vectors"), _need(t, "t"), _need(loc, "loc"), _need(vel, "vel")
+    R, cloc, cvel = torch.empty_like(v), torch.empty_like(loc), torch.empty_like(vel)
+    with torch.cuda.device(v.device):
+        st = lib.eqa_nbody_frame_fwd(v.data_ptr(), t.data_ptr(), loc.data_ptr(), vel.data_ptr(), R.data_ptr(), cloc.data_ptr(),
+                                     cvel.data_ptr(), M, _stream())
+    _lib.check(st, "eqa_nbody_frame_fwd")
+    return R, cloc, cvel
+
+
+def nbody_frame_bwd(v: torch.Tensor, t: Optional[torch.Tensor], loc: Optional[torch.Tensor], vel: Optional[torch.Tensor],
+                    R: Optional[torch.Tensor], gR: Optional[torch.Tensor], gcloc: Optional[torch.Tensor],
+                    gcvel: Optional[torch.Tensor], need: Tuple[bool, bool, bool, bool] = (True, True, True, True)
+                    ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Backward of `nbody_frame_fwd` in one launch (eqa_nbody_frame_bwd): incoming gR:(M,3,3), gcloc, gcvel:(M,3), each None for
+    zero -> (gv, gt, gloc, gvel), None where ``need`` says not wanted.  With gcloc = gcvel = None and need = (True, False, False,
+    False) it is the backward of `modified_gram_schmidt`, and t, loc, vel, R may be None."""
+    if v is None:
+        raise TypeError("vectors must be a torch.Tensor")
+    M = _rows("nbody_frame_bwd", None, vectors=(v, (3, 3)), t=(t, (3,)), loc=(loc, (3,)), vel=(vel, (3,)), R=(R, (3, 3)),
+              gR=(gR, (3, 3)), gcloc=(gcloc, (3,)), gcvel=(gcvel, (3,)))
+    need_v, need_t, need_loc, need_vel = (bool(n) for n in need)
+    if not (need_v or need_t or need_loc or need_vel):
+        raise ValueError("nbody_frame_bwd: no gradient wanted")
+    if (need_t or need_loc or need_vel) and R is None:
+        raise ValueError("nbody_frame_bwd: gt, gloc and gvel need the frame R the forward returned")
+    if need_v and ((gcloc is not None and (loc is None or t is None)) or (gcvel is not None and vel is None)):
+        raise ValueError("nbody_frame_bwd: gv needs loc and t with gcloc, vel with gcvel")
+    lib = _lib.load()
+    v = _need(v, "vectors")
+    t, p_t = _opt(t, "t", torch.float32)
+    loc, p_loc = _opt(loc, "loc", torch.float32)
+    vel, p_vel = _opt(vel, "vel", torch.float32)
+    R, p_R = _opt(R, "R", torch.float32)
+    gR, p_gR = _opt(gR, "gR", torch.float32)
+    gcloc, p_gcloc = _opt(gcloc, "gcloc", torch.float32)
+    gcvel, p_gcvel = _opt(gcvel, "gcvel", torch.float32)
+    new = lambda shape: torch.empty(shape, dtype=torch.float32, device=v.device)      # noqa: E731
+    gv = new((M, 3, 3)) if need_v else None
+    gt, gloc, gvel = (new((M, 3)) if n else None for n in (need_t, need_loc, need_vel))
+    ptr = lambda x: None if x is None else x.data_ptr()                               # noqa: E731
+    with torch.cuda.device(v.device):
+        st = lib.eqa_nbody_frame_bwd(v.data_ptr(), p_t, p_loc, p_vel, p_R, p_gR, p_gcloc, p_gcvel, ptr(gv), ptr(gt), ptr(gloc),
+                                     ptr(gvel), M, _stream())
+    _lib.check(st, "eqa_nbody_frame_bwd")
+    return gv, gt, gloc, gvel
+
+
+def rigid_rows_bwd(x: Optional[torch.Tensor], R: Optional[torch.Tensor], g: torch.Tensor, need: Tuple[bool, bool] = (True, True)
+                   ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Backward of `rigid_rows(x, R, t, inverse=False)` (eqa_rigid_rows_bwd): g:(M,3) -> (gx = g R^T, gR[i][j] = x_i g_j), None
+    where ``need`` says not wanted.  The gradient of t is g itself."""
+    if g is None:
+        raise TypeError("g must be a torch.Tensor")
+    M = _rows("rigid_rows_bwd", None, g=(g, (3,)), x=(x, (3,)), R=(R, (3, 3)))
+    need_x, need_R = bool(need[0]), bool(need[1])
+    if not (need_x or need_R) or (need_x and R is None) or (need_R and x is None):
+        raise ValueError("rigid_rows_bwd: gx needs R, gR needs x, and one of the two must be wanted")
+    lib = _lib.load()
+    g = _need(g, "g")
+    x, p_x = _opt(x, "x", torch.float32)
+    R, p_R = _opt(R, "R", torch.float32)
+    gx = torch.empty_like(g) if need_x else None
+    gR = torch.empty((M, 3, 3), dtype=torch.float32, device=g.device) if need_R else None
+    with torch.cuda.device(g.device):
+        st = lib.eqa_rigid_rows_bwd(p_x, p_R, g.data_ptr(), None if gx is None else gx.data_ptr(),
+                                    None if gR is None else gR.data_ptr(), M, _stream())
+    _lib.check(st, "eqa_rigid_rows_bwd")
+    return gx, gR
+
+
+FOURIER_FIELD_DIM = 9  # channels of a band-limited SO(2) field: a_0, (Re, Im) c_1..c_4 (csrc/fourier_act.hip)
 
 
 def _fourier_args(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], what: str):

@@ -792,6 +792,29 @@ int eqa_modified_gram_schmidt(const float* v, float* out, int B, void* stream);
 int eqa_rigid_rows(const float* x, const float* R, const float* t, float* out, int M, int mode, void* stream);
 
 /*
+ * (f).4, training -- the canonicalizer's frame chain in one launch each way (euclidean_group.py:87-124 canonicalize with :139-157
+ * modified_gram_schmidt, and the autograd graph torch records through them; :126-137 invert_canonicalization for the last entry).
+ * One thread per node, plain loads and stores, nothing summed across nodes: two launches on the same input give the same bits, and a
+ * degenerate frame (zero first vector, collinear vectors: non-finite in the reference as well) stays in its own row.
+ *   eqa_nbody_frame_fwd   v:(M,3,3), t, loc, vel:(M,3) -> R = MGS(v) (rows), cloc = loc R^T - t R^T, cvel = vel R^T: the bits of
+ *                         eqa_modified_gram_schmidt followed by eqa_rigid_rows mode 1 with t and mode 1 without (R rounded to fp32
+ *                         before it is applied)
+ *   eqa_nbody_frame_bwd   incoming gR:(M,3,3), gcloc, gcvel:(M,3), each NULL for zero; outgoing gv:(M,3,3), gt, gloc, gvel:(M,3), each
+ *                         NULL for not wanted (at least one is).  gloc = gcloc R, gt = -gloc, gvel = gcvel R with the R given;
+ *                         gv = the reverse pass of the modified Gram-Schmidt on G[j,:] = gR[j,:] + gcloc_j (loc - t) + gcvel_j vel,
+ *                         in fp64 with the intermediates recomputed from v, rounded once.  R is read only for gt / gloc / gvel; t, loc
+ *                         (vel) only for gv with gcloc (gcvel).  gcloc = gcvel = NULL: the backward of eqa_modified_gram_schmidt.
+ *   eqa_rigid_rows_bwd    of eqa_rigid_rows mode 0: g:(M,3) -> gx = g R^T, gR[i][j] = x_i g_j, either NULL for not wanted (gt is g)
+ * A NULL pointer that is read, M < 0, no output wanted: EQA_ERR_INVALID_ARG.
+ * Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_nbody_frame_fwd(const float* v, const float* t, const float* loc, const float* vel, float* R, float* cloc, float* cvel, int M,
+                        void* stream);
+int eqa_nbody_frame_bwd(const float* v, const float* t, const float* loc, const float* vel, const float* R, const float* gR,
+                        const float* gcloc, const float* gcvel, float* gv, float* gt, float* gloc, float* gvel, int M, void* stream);
+int eqa_rigid_rows_bwd(const float* x, const float* R, const float* g, float* gx, float* gR, int M, void* stream);
+
+/*
  * FourierELU over band-limited SO(2) fields, fused with a per-field affine map (ESCNNSteerableNetwork: the hidden activation and,
  * in eval mode, the field norm in front of it; reference network: escnn_networks.py:120-224, e2cnn FourierELU with N = 16 over
  * irreps 0..4).  x, y, dy, dx: channels-last (npix, 9 * fields) fp32, 16-byte aligned; channel 9 c + j is coefficient j of field c:

@@ -7,6 +7,9 @@ events after a warm-up, median over the rounds:
   train       train mode: forward (each route draws its own dropout mask), a linear loss, backward to the parameters
   edges       the fused inference call with the cached pair of complete_graph_edges (hit) against freshly cloned edge tensors every
               call (miss: adjacency kernel + one 4-byte read back)
+  canonicalizer step   EuclideanGroupNBody(VNDeepSets) in train mode: forward, invert_canonicalization of a prediction made from the
+              canonical coordinates, a linear loss, backward to the parameters; the network on its fused route both times, the frame
+              chain behind it on its kernels against EQA_NBODY_FRAME_KERNEL=0 (op by op)
 and the number of device launches (kernels, fills, copies) per call of both routes, counted by torch.profiler.
 One JSON line per (size, leg).  --small: S = 8 and few calls, to rehearse the script."""
 import json
@@ -113,4 +116,26 @@ for S in SIZES:
     med, spread = alternate({"hit": lambda: infer(True), "miss": miss}, N, ROUNDS)
     print(json.dumps({"S": S, "leg": "edges", "hit_ms": med["hit"], "miss_ms": med["miss"], "miss_costs_ms": med["miss"] - med["hit"],
                       "launches_hit": launches(lambda: infer(True)), "launches_miss": launches(miss), "min_max_ms": spread}))
+
+    os.environ["EQA_NBODY_KERNEL"] = "1"
+    can = ea.EuclideanGroupNBody(net)
+    nodes = torch.ones(M, 1, device=dev)
+    w1, w2, w3 = torch.randn(M, 3, device=dev), torch.randn(M, 3, device=dev), torch.randn(M, 3, device=dev)
+
+    def step(kernel):
+        os.environ["EQA_NBODY_FRAME_KERNEL"] = "1" if kernel else "0"
+        net.train()
+        for p in net.parameters():
+            p.grad = None
+        cloc, cvel = can(nodes, loc=loc, edges=edges, vel=vel, edge_attr=None, charges=charges)
+        back = can.invert_canonicalization(0.5 * cloc + cvel)
+        routes["step fused" if kernel else "step plain"] = [net.last_route, can.last_route, can.last_invert_route]
+        ((cloc * w1).sum() + (cvel * w2).sum() + (back * w3).sum()).backward()
+
+    med, spread = alternate({"fused": lambda: step(True), "plain": lambda: step(False)}, N, ROUNDS)
+    print(json.dumps({"S": S, "leg": "canonicalizer step", "fused_ms": med["fused"], "plain_ms": med["plain"],
+                      "speedup": med["plain"] / med["fused"], "launches_fused": launches(lambda: step(True)),
+                      "launches_plain": launches(lambda: step(False)), "min_max_ms": spread,
+                      "routes": {k: v for k, v in routes.items() if k.startswith("step")}}))
 os.environ.pop("EQA_NBODY_KERNEL", None)
+os.environ.pop("EQA_NBODY_FRAME_KERNEL", None)

@@ -39,6 +39,9 @@ from equiadapt_amd.images.canonicalization_networks import (  # noqa: F401
     CustomEquivariantNetwork,
     ESCNNEquivariantNetwork,
     ESCNNSteerableNetwork,
+    ESCNNWideBasic,
+    ESCNNWideBottleneck,
+    ESCNNWRNEquivariantNetwork,
     RotationEquivariantConv,
     RotationEquivariantConvLift,
     RotoReflectionEquivariantConv,
@@ -94,6 +97,8 @@ __all__ = [
     "EuclideanGroupNBody", "VNDeepSets", "flip_boxes", "flip_masks", "roll_by_gather", "rotate_boxes", "rotate_masks", "rotate_points",
     # the rest of the reference's vector_neuron_layers.py (in the reference's __all__)
     "VNBilinear", "VNLeakyReLU", "VNLinear", "VNSoftplus", "VNStdFeature",
+    # the wide-ResNet canonicalization network and its blocks (escnn_networks.py:228-511; in the reference's __all__)
+    "ESCNNWRNEquivariantNetwork", "ESCNNWideBasic", "ESCNNWideBottleneck",
 ]
 
 __version__ = "0.1.0"

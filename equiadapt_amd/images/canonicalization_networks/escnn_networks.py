@@ -635,3 +635,11 @@ class ESCNNEquivariantNetwork(nn.Module):
         else:
             fm = self.eqv_network(x)
         return group_pool(fm)
+
+
+# (reference: same module; at the end because wrn_networks takes _InnerBatchNorm from this one)
+from equiadapt_amd.images.canonicalization_networks.wrn_networks import (  # noqa: E402,F401
+    ESCNNWideBasic,
+    ESCNNWideBottleneck,
+    ESCNNWRNEquivariantNetwork,
+)

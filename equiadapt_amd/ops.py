@@ -1371,3 +1371,64 @@ def vn_act_backward(x: torch.Tensor, Wd: torch.Tensor, gy: torch.Tensor, softplu
                                 int(softplus), slope, _stream())
     _lib.check(st, "eqa_vn_act_bwd")
     return gx, partial.sum(0)
+
+
+def gconv1x1_supported(pixels: int, cin: int, cout: int) -> bool:
+    """Shapes and sizes eqa_gconv1x1_nhwc takes: channel counts on the multiples of 32 from 32 to 512, every map inside one 32-bit
+    buffer range (the size is part of the query: a caller that asks first takes its other route instead of failing in the launch)."""
+    return bool(_lib.load().eqa_gconv1x1_supported(pixels, cin, cout))
+
+
+def pack_gconv1x1_weights(bank: torch.Tensor) -> torch.Tensor:
+    """(Cout, Cin) or (Cout, Cin, 1, 1) filters of a 1 x 1 convolution -> the MFMA operand-fragment order of eqa_gconv1x1_nhwc:
+    Wpk[s][n][b][32 h + i][t] = bank[32 n + i][16 s + 8 b + 4 h + t]  (`pack_plane_gemm_weights` of the one plane bank^T)."""
+    Cout, Cin = bank.shape[:2]
+    if bank.numel() != Cout * Cin:
+        raise ValueError(f"pack_gconv1x1_weights takes the filters of a 1 x 1 convolution, got {tuple(bank.shape)}")
+    return pack_plane_gemm_weights(bank.reshape(Cout, Cin).t()[None])[0]
+
+
+def gconv1x1_nhwc(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, res: Optional[torch.Tensor] = None,
+                  scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """y = act(conv1x1(x) + bias [+ res]), act(z) = [relu](scale[c] * z + shift[c]), one launch (eqa_gconv1x1_nhwc).  x: a
+    channels-last (B, Cin, H, W) map or its (pixels, Cin) matrix; res and the result likewise with Cout channels;
+    wpk = pack_gconv1x1_weights(filters); scale and shift together or not at all.  No autograd."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise RuntimeError("gconv1x1_nhwc expects an fp32 tensor on the device")
+    wpk = _need(wpk, "wpk")
+    Cin, Cout = wpk.shape[0] * 16, wpk.shape[1] * 32
+
+    def rows(t, name, C):
+        if t.dim() == 4:
+            if t.shape[1] != C or not t.is_contiguous(memory_format=torch.channels_last):
+                raise RuntimeError(f"gconv1x1_nhwc: {name} must be a channels-last map of {C} channels, got {tuple(t.shape)}")
+            return t.shape[0] * t.shape[2] * t.shape[3]
+        if t.dim() != 2 or t.shape[1] != C or not t.is_contiguous():
+            raise RuntimeError(f"gconv1x1_nhwc: {name} must be a contiguous (pixels, {C}) matrix, got {tuple(t.shape)}")
+        return t.shape[0]
+
+    P = rows(x, "x", Cin)
+    bias = _need(bias, "bias")
+    if (scale is None) != (shift is None):
+        raise ValueError("gconv1x1_nhwc: scale and shift come together")
+    scale, p_scale = _opt(scale, "scale", torch.float32)
+    shift, p_shift = _opt(shift, "shift", torch.float32)
+    if any(v is not None and v.numel() != Cout for v in (bias, scale, shift)):
+        raise ValueError(f"gconv1x1_nhwc: bias, scale and shift have {Cout} entries")
+    p_res = None
+    if res is not None:
+        if res.dtype != torch.float32 or res.device != x.device or rows(res, "res", Cout) != P or res.dim() != x.dim():
+            raise RuntimeError("gconv1x1_nhwc: res must be an fp32 map of the output's shape and layout on x's device")
+        p_res = res.data_ptr()
+    if not gconv1x1_supported(P, Cin, Cout):
+        raise _lib.EqaLibraryError(f"eqa_gconv1x1_nhwc does not take {P} pixels of {Cin} -> {Cout} channels (ask gconv1x1_supported first)")
+    if x.dim() == 4:
+        y = torch.empty((x.shape[0], Cout, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    else:
+        y = torch.empty((P, Cout), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("gconv1x1"):
+        st = lib.eqa_gconv1x1_nhwc(x.data_ptr(), wpk.data_ptr(), bias.data_ptr(), p_res, p_scale, p_shift, int(relu), y.data_ptr(), P, Cin, Cout,
+                                   _stream())
+    _lib.check(st, "eqa_gconv1x1_nhwc")
+    return y

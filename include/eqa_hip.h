@@ -887,6 +887,24 @@ int eqa_vn_act_fwd(const float* x, const float* Wd, float* y, int B, int C, long
 int eqa_vn_act_bwd(const float* x, const float* Wd, const float* gy, float* gx, float* partial, int B, int C, long long P, int D,
                    int softplus, float slope, void* stream);
 
+/*
+ * The 1 x 1 group convolutions of the wide-ResNet canonicalization network's bottleneck block on a channels-last map
+ * (equiadapt/images/canonicalization_networks/escnn_networks.py:262 and :270, R2Conv(.., 1); :283-285, `out += x`; :474-479, the
+ * InnerBatchNorm + ReLU behind the block), as one GEMM over the pixels on the fp32 MFMA with those passes in its epilogue:
+ *   z[p][o] = sum_c x[p][c] W[c][o] + bias[o] (+ res[p][o]),   y[p][o] = relu ? max(s[o] z + t[o], 0) : s[o] z + t[o]
+ * x:(P,Cin); res, y:(P,Cout); bias, s, t:(Cout); res NULL: no residual; s and t NULL together: the identity.  y aliases neither x
+ * nor res.  Wpk: W:(Cin,Cout) re-ordered into MFMA operand fragments as for eqa_plane_gemm with one plane,
+ *   Wpk[s][n][b][32 h + i][t] = W[16 s + 8 b + 4 h + t][32 n + i]     (Cin/16, Cout/32, 2, 64, 4)
+ * eqa_gconv1x1_supported: Cin, Cout multiples of 32 in [32, 512], and P * max(Cin, Cout) * 4 bytes within one 32-bit buffer
+ * range (<= 0xffffff00) -- the size test is part of the query, so a caller that asks first never meets EQA_ERR_UNSUPPORTED from the
+ * launch for a size.  Pointers 16-byte aligned (else EQA_ERR_UNSUPPORTED).  Rows >= P are never written.  P = 0: nothing is launched.
+ * fmaf chains over c in a fixed order: two launches on the same input give the same bits.  No gradient.
+ * Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_gconv1x1_supported(long long P, int Cin, int Cout);
+int eqa_gconv1x1_nhwc(const float* x, const float* Wpk, const float* bias, const float* res, const float* s, const float* t, int relu,
+                      float* y, long long P, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

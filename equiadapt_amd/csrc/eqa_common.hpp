@@ -84,7 +84,7 @@ struct QuadWalk {
 };
 
 extern int g_force_direct;     // group_action.hip; eqa_set_option key 0 (forced direct gathers / the row-per-block nearest kernel)
-extern int g_vn_kernel_choice;  // pointcloud.hip; eqa_set_option key 1
+extern int g_vn_kernel_choice;  // vnsmall_fwd.hip; eqa_set_option key 1
 extern int g_cgemm_bf16_form;   // cgemm3m_bf16.hip; eqa_set_option key 2
 
 // Counter-based hash for the dropout mask of the canonicalization network's hidden blocks (one draw per element, reproducible from

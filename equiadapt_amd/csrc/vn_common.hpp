@@ -1,10 +1,26 @@
-// Shared device code of the VNSmall kernels (pointcloud.hip: fused eval forward; vnsmall_train.hip: training passes).
+// Shared device code of the vector-neuron kernels: vnsmall_fwd.hip (fused eval forward), vnsmall_train.hip and vnsmall_tail.hip
+// (training passes), vn_act.hip (activation layers), pointcloud.hip (Gram-Schmidt).
 #pragma once
 #include "eqa_common.hpp"
 
 namespace {
 
-constexpr int kVnC = 21, kVnK = 20, kVnThreads = 128, kVnParams = 1310;
+constexpr int kVnC = 21, kVnK = 20, kVnThreads = 128;
+
+// The packed parameter buffer of the fused eval forward (eqa_vnsmall_fwd, VNSmall.packed_parameters), floats, eval-mode
+// batch-norms pre-folded to scale/shift of the vector NORM:
+//   [0,63) pos.Wf(21x3)  [63,126) pos.Wd  [126,147) pos.bn scale  [147,168) pos.bn shift
+//   [168,609) c1.Wf(21x21)  [609,1050) c1.Wd  [1050,1071) c1.bn scale  [1071,1092) c1.bn shift  [1092,1113) bn1 scale  [1113,1134) bn1 shift
+//   [1134,1218) c2.Wf(4x21)  [1218,1302) c2.Wd  [1302,1306) c2.bn scale  [1306,1310) c2.bn shift
+//   pooling = "max" only: [1310,1751) pool.Wd(21x21)
+namespace vn_prm {
+constexpr int pos_wf = 0, pos_wd = pos_wf + kVnC * 3, pos_scale = pos_wd + kVnC * 3, pos_shift = pos_scale + kVnC;
+constexpr int c1_wf = pos_shift + kVnC, c1_wd = c1_wf + kVnC * kVnC, c1_scale = c1_wd + kVnC * kVnC, c1_shift = c1_scale + kVnC;
+constexpr int bn1_scale = c1_shift + kVnC, bn1_shift = bn1_scale + kVnC;
+constexpr int c2_wf = bn1_shift + kVnC, c2_wd = c2_wf + 4 * kVnC, c2_scale = c2_wd + 4 * kVnC, c2_shift = c2_scale + 4;
+constexpr int pool_wd = c2_shift + 4, end_max = pool_wd + kVnC * kVnC;
+static_assert(pool_wd == EQA_VNSMALL_PARAMS && end_max == EQA_VNSMALL_PARAMS_MAX, "packed layout and include/eqa_hip.h disagree");
+}  // namespace vn_prm
 #ifndef EQA_VN_MIN_BLOCKS
 #define EQA_VN_MIN_BLOCKS 3  // waves per SIMD the register allocation must allow (measured 2: 481 k, 3: 531 k, 4: 416 k clouds/s)
 #endif
@@ -48,6 +64,35 @@ __device__ __forceinline__ V3 vn_relu_sel(V3 q, const V3& d) {
   const float dp = dot3(q, d);
   const float t = dp < 0.0f ? vn_div(dp, dot3(d, d) + kVnEps) : 0.0f;
   return v3(q.x - t * d.x, q.y - t * d.y, q.z - t * d.z);
+}
+
+// edge features of (centre, neighbour): [neighbour - centre, centre, neighbour x centre]
+struct VnEdge {
+  V3 f0, f1, f2;
+};
+__device__ __forceinline__ VnEdge vn_edge(const V3& ctr, const float4& nb4) {
+  const V3 nb = v3(nb4.x, nb4.y, nb4.z);
+  VnEdge e;
+  e.f0 = v3(nb.x - ctr.x, nb.y - ctr.y, nb.z - ctr.z);
+  e.f1 = ctr;
+  e.f2 = v3(nb.y * ctr.z - nb.z * ctr.y, nb.z * ctr.x - nb.x * ctr.z, nb.x * ctr.y - nb.y * ctr.x);
+  return e;
+}
+__device__ __forceinline__ V3 vn_mix(const float* __restrict__ w, const VnEdge& e) {  // w[0..2]: one output channel
+  return v3(w[0] * e.f0.x + w[1] * e.f1.x + w[2] * e.f2.x, w[0] * e.f0.y + w[1] * e.f1.y + w[2] * e.f2.y,
+            w[0] * e.f0.z + w[1] * e.f1.z + w[2] * e.f2.z);
+}
+// vn_mix with the centre's term c1 = w[1] * e.f1 formed once for all edges of a point.  (w0 f0 + c1) + w2 f2 contracts to other
+// fused multiply-adds than vn_mix's sum, so the bits differ: the quad eval kernel's mean branch has always had this form.
+__device__ __forceinline__ V3 vn_mix_hoisted(float w0, const V3& c1, float w2, const VnEdge& e) {
+  return v3(w0 * e.f0.x + c1.x + w2 * e.f2.x, w0 * e.f0.y + c1.y + w2 * e.f2.y, w0 * e.f0.z + c1.z + w2 * e.f2.z);
+}
+
+// One output vector of conv_pos in the training passes: h_c = gate(bn(W_f[c] e), W_d[c] e), the gate without a branch.  (The eval
+// loops gate with vn_relu and call vn_mix / vn_bn / vn_relu themselves: through this function their scalar loads are scheduled differently.)
+__device__ __forceinline__ V3 vn_convpos_h(const float* __restrict__ wf, const float* __restrict__ wd, float scale, float shift,
+                                           const VnEdge& e) {
+  return vn_relu_sel(vn_bn(vn_mix(wf, e), scale, shift), vn_mix(wd, e));
 }
 
 // Backward of one VN layer output  y = gate(u * nbn, d),  u = q / n,  n = |q| + EPS,  nbn = n * scale + shift  (scale = gamma *
@@ -112,9 +157,11 @@ __device__ __forceinline__ V3 vn_norm_input_grad(const VnGrad& r, float sc, floa
             (g_u.z - r.u.z * proj) * inv_n + gq * r.q.z);
 }
 
-// A cloud staged in LDS as float4 (x, y, z, |p|^2): one ds_read_b128 per kNN candidate.  x: (3, N) of one cloud.
+// A cloud staged in LDS as float4 (x, y, z, |p|^2): one ds_read_b128 per kNN candidate.  x: (3, N) of one cloud, padded to Npad
+// with never-selected points (a multiple of 4, or of 16 for the quad kernels), by a block of THREADS threads.
+template <int THREADS>
 __device__ __forceinline__ void vn_stage_cloud(const float* __restrict__ xb, int N, int Npad, float4* pts, int tid) {
-  for (int i = tid; i < Npad; i += kVnThreads) {
+  for (int i = tid; i < Npad; i += THREADS) {
     if (i < N) {
       const float a = xb[i], c = xb[N + i], d = xb[2 * (size_t)N + i];
       pts[i] = make_float4(a, c, d, a * a + c * c + d * d);  // torch.sum(x**2, dim=1)
@@ -233,18 +280,6 @@ __device__ __forceinline__ float vn_quad_sum(float v) {
   return v;
 }
 
-// cloud -> LDS as float4 (x, y, z, |p|^2), padded with never-selected points to a multiple of 16
-__device__ __forceinline__ void vn_stage_cloud_quad(const float* __restrict__ xb, int N, int Npad, float4* pts, int tid) {
-  for (int i = tid; i < Npad; i += kVnQThreads) {
-    if (i < N) {
-      const float a = xb[i], c = xb[N + i], d = xb[2 * (size_t)N + i];
-      pts[i] = make_float4(a, c, d, a * a + c * c + d * d);
-    } else {
-      pts[i] = make_float4(0.f, 0.f, 0.f, INFINITY);
-    }
-  }
-}
-
 // The point's 4 SEG nearest neighbours, distributed: on return lane `sub` of the quad holds ranks [SEG sub, SEG sub + SEG) in
 // (bv, bi), best first.  queue: LDS, [kVnQSlots][kVnQThreads] float2, this BLOCK's base.
 template <int SEG>
@@ -322,6 +357,31 @@ __device__ __forceinline__ void vn_knn_quad(const float4* pts, int Npad, float2*
     if (__any(cnt > kVnQSlots - 4)) drain();  // wave-uniform
   }
   drain();
+}
+
+// classical Gram-Schmidt of the three rows of p -> o (both 9 floats): gram_schmidt_kernel (pointcloud.hip), vnsmall_canon_tail_kernel
+__device__ __forceinline__ void gram_schmidt_rows(const float* p, float* o) {
+  // The three steps of common/utils.py:22-51 (no epsilon, no handedness fix) evaluated in fp64 and rounded once: 9 numbers per
+  // cloud, so the cost is nil, and the step has no epsilon -- it amplifies rounding by the conditioning of the three vectors
+  // (cond 540 on one of the bench's eight clouds, 1,659 among 64: an fp32 evaluation, this one or the reference's, then sits
+  // 4e-5 .. 6e-5 from the exact frame; tools/cfg4_budget.py).  In fp64 the frame is the exact Gram-Schmidt of the vectors the
+  // network kernel produced, to the last fp32 bit, so the only error left in R is the network's own, amplified.
+  double a0 = p[0], a1 = p[1], a2 = p[2], b0 = p[3], b1 = p[4], b2 = p[5], c0 = p[6], c1 = p[7], c2 = p[8];
+  double n = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+  a0 /= n; a1 /= n; a2 /= n;
+  const double d = b0 * a0 + b1 * a1 + b2 * a2;
+  b0 -= d * a0; b1 -= d * a1; b2 -= d * a2;
+  n = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+  b0 /= n; b1 /= n; b2 /= n;
+  const double d1 = c0 * a0 + c1 * a1 + c2 * a2;
+  const double d2 = c0 * b0 + c1 * b1 + c2 * b2;  // classical GS: both projections use the ORIGINAL c
+  c0 = c0 - d1 * a0 - d2 * b0;
+  c1 = c1 - d1 * a1 - d2 * b1;
+  c2 = c2 - d1 * a2 - d2 * b2;
+  n = sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+  c0 /= n; c1 /= n; c2 /= n;
+  o[0] = (float)a0; o[1] = (float)a1; o[2] = (float)a2; o[3] = (float)b0; o[4] = (float)b1; o[5] = (float)b2;
+  o[6] = (float)c0; o[7] = (float)c1; o[8] = (float)c2;
 }
 
 }  // namespace

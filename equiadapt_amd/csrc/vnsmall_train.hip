@@ -22,29 +22,7 @@
 
 namespace {
 
-// edge features of (centre, neighbour): [neighbour - centre, centre, neighbour x centre]
-struct VnEdge {
-  V3 f0, f1, f2;
-};
-__device__ __forceinline__ VnEdge vn_edge(const V3& ctr, const float4& nb4) {
-  const V3 nb = v3(nb4.x, nb4.y, nb4.z);
-  VnEdge e;
-  e.f0 = v3(nb.x - ctr.x, nb.y - ctr.y, nb.z - ctr.z);
-  e.f1 = ctr;
-  e.f2 = v3(nb.y * ctr.z - nb.z * ctr.y, nb.z * ctr.x - nb.x * ctr.z, nb.x * ctr.y - nb.y * ctr.x);
-  return e;
-}
-__device__ __forceinline__ V3 vn_mix(const float* __restrict__ w, const VnEdge& e) {  // w[0..2]: one output channel
-  return v3(w[0] * e.f0.x + w[1] * e.f1.x + w[2] * e.f2.x, w[0] * e.f0.y + w[1] * e.f1.y + w[2] * e.f2.y,
-            w[0] * e.f0.z + w[1] * e.f1.z + w[2] * e.f2.z);
-}
-
-// One output vector of the block's forward: h_c = gate(bn(W_f[c] e), W_d[c] e)
-__device__ __forceinline__ V3 vn_convpos_h(const float* __restrict__ wf, const float* __restrict__ wd, float scale, float shift,
-                                           const VnEdge& e) {
-  return vn_relu_sel(vn_bn(vn_mix(wf, e), scale, shift), vn_mix(wd, e));
-}
-
+// (the edge features VnEdge / vn_edge / vn_mix and conv_pos's output vector vn_convpos_h: vn_common.hpp, shared with the eval kernels)
 // block-wide sum of NV per-thread values -> out[0..NV) (deterministic: shuffles, then a fixed-order sum over the waves)
 template <int NV>
 __device__ __forceinline__ void vn_block_sum(float (&v)[NV], float* s_red /* [waves][NV] */, float* __restrict__ out) {
@@ -91,7 +69,7 @@ __global__ __launch_bounds__(kVnQThreads, 4) void vn_knn_kernel(const float* __r
   float4* pts = reinterpret_cast<float4*>(vn_smem);
   const int b = blockIdx.y, tid = threadIdx.x, sub = tid & 3;
   const int Npad = (N + 15) & ~15;
-  vn_stage_cloud_quad(x + (size_t)b * 3 * N, N, Npad, pts, tid);
+  vn_stage_cloud<kVnQThreads>(x + (size_t)b * 3 * N, N, Npad, pts, tid);
   __syncthreads();
   const int n = blockIdx.x * kVnQPts + (tid >> 2);
   const bool active = n < N;
@@ -121,7 +99,7 @@ constexpr int kVnSplit = 4, kVnPts = kVnThreads / kVnSplit;
   float4* pts = reinterpret_cast<float4*>(vn_smem);                                                \
   const int b = blockIdx.y, tid = threadIdx.x;                                                     \
   const int Npad = (N + 3) & ~3;                                                                   \
-  vn_stage_cloud(x + (size_t)b * 3 * N, N, Npad, pts, tid);                                        \
+  vn_stage_cloud<kVnThreads>(x + (size_t)b * 3 * N, N, Npad, pts, tid);                            \
   __syncthreads();                                                                                 \
   const int n = blockIdx.x * kVnPts + tid / kVnSplit, sub = tid % kVnSplit;                        \
   const bool active = n < N;                                                                       \
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_stats_kernel(const floa
   float acc[2 * kVnC];
 #pragma unroll
   for (int c = 0; c < kVnC; ++c) {
-    asm volatile("" ::: "memory");  // one channel at a time (see pointcloud.hip)
+    asm volatile("" ::: "memory");  // one channel at a time (see vnsmall_fwd.hip)
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int t = 0; t < EMAX; ++t) {
@@ -192,16 +170,11 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_fwd_kernel(const float*
   }
   // the four lanes of a point: butterfly over the quad, every lane ends up with the point's sums; lane `sub` stores channels
   // c = sub, sub + 4, ...
-  auto quad_sum = [](float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));  // [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false));  // [2,3,0,1]
-    return v;
-  };
   const float inv_k = 1.0f / (float)k;
   float* o = pooled + (size_t)b * kVnC * 3 * N + (active ? n : N - 1);  // (B, 21, 3, N)
 #pragma unroll
   for (int c = 0; c < kVnC; ++c) {
-    const float sx = quad_sum(acc[c].x), sy = quad_sum(acc[c].y), sz = quad_sum(acc[c].z);
+    const float sx = vn_quad_sum(acc[c].x), sy = vn_quad_sum(acc[c].y), sz = vn_quad_sum(acc[c].z);
     if (active && (c % kVnSplit) == sub) {
       o[(size_t)(3 * c) * N] = sx * inv_k;
       o[(size_t)(3 * c + 1) * N] = sy * inv_k;
@@ -211,8 +184,9 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_fwd_kernel(const float*
 }
 
 // The quad's best (score, list position) of one channel, to all four lanes: the larger score, on equal scores the lower position
-// (the first maximum of the list, torch.max's; the rule of the fused eval kernel, pointcloud.hip).  A lane without a live edge
-// holds (-inf, 255) and never wins.
+// (the first maximum of the list, torch.max's).  A lane without a live edge holds (-inf, 255) and never wins.  This merge carries
+// list positions and compares them; the fused eval kernel's (vnsmall_fwd.hip) has none and decides equal scores by lane parity
+// ('>=' towards the lower lane, '>' towards the higher), so the two stay separate.
 template <int CTRL>
 __device__ __forceinline__ void vn_quad_better(float& s, int& p) {
   const float os = vn_dpp_f<CTRL>(s);
@@ -243,7 +217,7 @@ __global__ __launch_bounds__(kVnThreads) void vn_convpos_max_fwd_kernel(const fl
   }
 #pragma unroll 1
   for (int t = 0; t < edges; ++t) {      // lane 0 of every quad owns `edges` positions: wave-uniform trip count
-    asm volatile("" ::: "memory");       // keep the weights in the scalar cache, not hoisted into VGPRs (see pointcloud.hip)
+    asm volatile("" ::: "memory");       // keep the weights in the scalar cache, not hoisted into VGPRs (see vnsmall_fwd.hip)
     const bool live = active && t < cnt;
     const VnEdge e = vn_edge(ctr, pts[nbr[t < cnt ? t : 0]]);
     V3 h[kVnC];

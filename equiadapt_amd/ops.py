@@ -11,6 +11,8 @@ from equiadapt_amd import _lib
 
 
 MAX_WINDOW_K = 10   # == kMaxWinK (csrc/eqa_common.hpp): the largest window the window-sum kernels take (the linearised last layer)
+VNSMALL_PARAMS = 1310       # == EQA_VNSMALL_PARAMS (include/eqa_hip.h): packed VNSmall parameters, pooling "mean" (layout: csrc/vn_common.hpp)
+VNSMALL_PARAMS_MAX = 1751   # == EQA_VNSMALL_PARAMS_MAX: pooling "max", + the pooling layer's 21 x 21 direction map
 
 
 def _stream() -> int:
@@ -386,17 +388,23 @@ def gram_schmidt(v: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def vnsmall_forward(x: torch.Tensor, params: torch.Tensor, k: int = 20, pooling: str = "mean") -> torch.Tensor:
-    """P1+P2 fused: (B,3,N) point clouds + packed VNSmall parameters -> (B,3,3) equivariant vectors (eqa_vnsmall_fwd).
-    ``pooling`` "mean" (1310 packed floats) or "max" (1751: + the pooling layer's 21 x 21 direction map)."""
-    lib = _lib.load()
+def _vnsmall_args(what: str, x: torch.Tensor, params: torch.Tensor, pooling: str):
+    """The argument check of the two fused VNSmall ops -> (x, params, B, N)."""
     x = _need(x, "point_cloud")
     params = _need(params, "params")
     B, three, N = x.shape
     if pooling not in ("mean", "max"):
         raise ValueError(f"Pooling type {pooling} not supported")
-    if three != 3 or params.numel() != (1310 if pooling == "mean" else 1751):
-        raise ValueError("vnsmall_forward expects x:(B,3,N) and 1310 (mean) / 1751 (max) packed parameters")
+    if three != 3 or params.numel() != (VNSMALL_PARAMS if pooling == "mean" else VNSMALL_PARAMS_MAX):
+        raise ValueError(f"{what} expects x:(B,3,N) and {VNSMALL_PARAMS} (mean) / {VNSMALL_PARAMS_MAX} (max) packed parameters")
+    return x, params, B, N
+
+
+def vnsmall_forward(x: torch.Tensor, params: torch.Tensor, k: int = 20, pooling: str = "mean") -> torch.Tensor:
+    """P1+P2 fused: (B,3,N) point clouds + packed VNSmall parameters -> (B,3,3) equivariant vectors (eqa_vnsmall_fwd).
+    ``pooling`` "mean" (1310 packed floats) or "max" (1751: + the pooling layer's 21 x 21 direction map)."""
+    lib = _lib.load()
+    x, params, B, N = _vnsmall_args("vnsmall_forward", x, params, pooling)
     out = torch.empty((B, 3, 3), dtype=torch.float32, device=x.device)
     ws = torch.empty((max(lib.eqa_vnsmall_workspace_bytes(B, N), 4) // 4,), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device), _timed("vnsmall_fwd"):
@@ -409,13 +417,7 @@ def vnsmall_canonicalize(x: torch.Tensor, params: torch.Tensor, k: int = 20, poo
     """P1-P4 in two launches (eqa_vnsmall_canonicalize): (B,3,N) clouds -> (network output vectors (B,3,3), their Gram-Schmidt
     frame R (B,3,3), canonical clouds R x (B,3,N))."""
     lib = _lib.load()
-    x = _need(x, "point_cloud")
-    params = _need(params, "params")
-    B, three, N = x.shape
-    if pooling not in ("mean", "max"):
-        raise ValueError(f"Pooling type {pooling} not supported")
-    if three != 3 or params.numel() != (1310 if pooling == "mean" else 1751):
-        raise ValueError("vnsmall_canonicalize expects x:(B,3,N) and 1310 (mean) / 1751 (max) packed parameters")
+    x, params, B, N = _vnsmall_args("vnsmall_canonicalize", x, params, pooling)
     vec = torch.empty((B, 3, 3), dtype=torch.float32, device=x.device)
     R = torch.empty((B, 3, 3), dtype=torch.float32, device=x.device)
     y = torch.empty_like(x)

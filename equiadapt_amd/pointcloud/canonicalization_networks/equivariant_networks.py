@@ -290,7 +290,7 @@ class VNSmall(nn.Module):
             raise ValueError(f"Pooling type {self.pooling} not supported")
 
     def packed_parameters(self) -> torch.Tensor:
-        """The 1310 floats the fused kernel consumes (layout: csrc/pointcloud.hip), eval-mode batch-norms folded to a
+        """The 1310 floats the fused kernel consumes (layout: vn_prm in csrc/vn_common.hpp), eval-mode batch-norms folded to a
         scale/shift of the vector norm; "max" pooling: + the 441 of the pooling layer's direction map.  Cached per parameter
         version."""
         tensors = list(self.parameters()) + [b for b in self.buffers()]
@@ -313,7 +313,9 @@ class VNSmall(nn.Module):
         if self.pooling == "max":
             parts.append(self.pool.map_to_dir.weight.flatten())
         packed = torch.cat([p.detach().float() for p in parts]).contiguous()
-        assert packed.numel() == (1751 if self.pooling == "max" else 1310)
+        from equiadapt_amd import ops
+
+        assert packed.numel() == (ops.VNSMALL_PARAMS_MAX if self.pooling == "max" else ops.VNSMALL_PARAMS)
         self._packed = (key, packed)
         return packed
 

@@ -676,7 +676,7 @@ int eqa_so3_rotate(const float* x, const float* R, float* y, int B, int N, int t
  * x:(B,3,N); out:(B,3,3) = mean over points of the first 3 output vector channels; 1 <= k <= 32 (and k <= N); pooling 0 = "mean",
  * 1 = "max" (VNMaxPool, vector_neuron_layers.py:327-364: per point and channel the edge maximising <x, W_p x>, first index on
  * ties like torch.max).
- * params: EQA_VNSMALL_PARAMS floats, batch-norms folded to scale/shift of the vector norm (layout in csrc/pointcloud.hip);
+ * params: EQA_VNSMALL_PARAMS floats, batch-norms folded to scale/shift of the vector norm (layout: vn_prm in csrc/vn_common.hpp);
  * pooling 1: + the 441 floats of the pooling layer's map_to_dir weight (EQA_VNSMALL_PARAMS_MAX in total).
  * workspace: eqa_vnsmall_workspace_bytes(B, N) bytes.  k > 32: EQA_ERR_UNSUPPORTED (the host keeps an op-by-op path).
  * Two kernels: four lanes per point (any k; the default) and one thread per point (k = 20; eqa_set_option key 1).

@@ -32,6 +32,9 @@ def test_library_exports_every_declared_symbol():
     from equiadapt_amd import ops
 
     assert _lib.load().eqa_get_option(100) == ops.MAX_WINDOW_K
+    header = open(os.path.join(ROOT, "include", "eqa_hip.h")).read()
+    assert ops.VNSMALL_PARAMS == int(re.search(r"#define\s+EQA_VNSMALL_PARAMS\s+(\d+)", header).group(1))
+    assert ops.VNSMALL_PARAMS_MAX == int(re.search(r"#define\s+EQA_VNSMALL_PARAMS_MAX\s+(\d+)", header).group(1))
     # argument validation happens before any device work, so it is checkable without a GPU
     assert _lib.load().eqa_set_option(99, 0) == -1
     assert _lib.load().eqa_group_pool_workspace_bytes(4, 32, 8, 7056) > 0

@@ -192,6 +192,9 @@ SIGNATURES = {
     "eqa_vn_act_bwd": (_int, [_vp] * 5 + [_int, _int, ctypes.c_longlong, _int, _int, ctypes.c_float, _vp]),
     "eqa_gconv1x1_supported": (_int, [ctypes.c_longlong, _int, _int]),
     "eqa_gconv1x1_nhwc": (_int, [_vp] * 6 + [_int, _vp, ctypes.c_longlong, _int, _int, _vp]),
+    "eqa_gconv1x1_wgrad_supported": (_int, [ctypes.c_longlong, _int, _int]),
+    "eqa_gconv1x1_wgrad_workspace_bytes": (ctypes.c_longlong, [ctypes.c_longlong, _int, _int]),
+    "eqa_gconv1x1_wgrad": (_int, [_vp] * 5 + [ctypes.c_longlong, _int, _int, _vp]),
 }
 
 _lock = threading.Lock()

@@ -10,10 +10,17 @@ InnerBatchNorm a BatchNorm3d over (B, fields, |G|, H, W).  Constructor, layer or
 field counts, kernel sizes, paddings and the output contract ((B, |G|) = mean over fields and space) are the reference's; the two
 block classes take field counts and the group instead of e2cnn ``FieldType``s.  A reference checkpoint does not load by key.
 
-Two routes (``net.last_routes``: one string per convolution, in module order -- a bottleneck's 1 x 1, k x k, 1 x 1; a basic block's
+Three routes (``net.last_routes``: one string per convolution, in module order -- a bottleneck's 1 x 1, k x k, 1 x 1; a basic block's
 two k x k and its shortcut -- naming what ran):
   plain   F.conv2d on the expanded banks, the batch-norm modules, ReLU, adds: any dtype and device the banks exist on, autograd,
-          training mode.  Every call in training mode or with gradients enabled takes it, and so does EQA_WRN_KERNEL=0.
+          training mode.  What neither of the other two takes runs here, and so does everything under EQA_WRN_KERNEL=0.
+  train   training mode or gradients enabled, fp32 on the device, channel counts on the multiples of 4, and at least one bottleneck
+          1 x 1 layer that the kernels take (`_train_ok`): channels-last throughout with autograd (`_forward_training`) -- the 1 x 1
+          layers on `GConv1x1Function` (eqa_gconv1x1_nhwc forward and data gradient, eqa_gconv1x1_wgrad filter and bias gradient;
+          the second one with the block input as the residual), the k x k layers on the Winograd / FFT convolution Functions, the
+          stem on LiftConvFunction, every InnerBatchNorm + ReLU on the fused batch-norm kernels, the tail as window sums; a layer
+          whose shape a kernel does not take runs on the library's convolution.  A network without an admitted bottleneck 1 x 1
+          layer (num_layers = 3; narrow ones) stays on the plain route.
   fused   eval mode, no_grad, fp32 on the device: channels-last throughout, the batch-norms behind a convolution folded into its
           bank; the two 1 x 1 convolutions of a bottleneck on eqa_gconv1x1_nhwc (csrc/gconv1x1.hip) -- the second with the residual
           add, the InnerBatchNorm behind the block and the ReLU in its epilogue: the junction is one launch --, the k x k layers on the
@@ -37,8 +44,48 @@ from equiadapt_amd.images.canonicalization_networks.custom_group_equivariant_lay
     RotoReflectionEquivariantConvLift,
     filter_action_matrices,
 )
-from equiadapt_amd.images.canonicalization_networks.escnn_networks import _InnerBatchNorm
-from equiadapt_amd.images.canonicalization_networks.pooling import conv_then_group_pool, group_pool
+from equiadapt_amd.images.canonicalization_networks.escnn_networks import (
+    ESCNNEquivariantNetwork,
+    InnerBnReluDropout,
+    LiftConvFunction,
+    _InnerBatchNorm,
+)
+from equiadapt_amd.images.canonicalization_networks.pooling import (
+    WindowSumsFunction,
+    WindowSumsLinearFn,
+    conv_then_group_pool,
+    group_pool,
+)
+
+
+class GConv1x1Function(torch.autograd.Function):
+    """y = conv1x1(x) + bias [+ res] on a channels-last map through eqa_gconv1x1_nhwc (the residual in its epilogue; no affine map, no
+    ReLU), with its gradients: dx = conv1x1(dy) with the transposed bank -- the same kernel on the packed transpose, zero bias --,
+    dbank and dbias from eqa_gconv1x1_wgrad, dres = dy.  Each only where it is needed.  bank: (Cout, Cin, 1, 1); bias: (Cout,).
+    The caller has asked `ops.gconv1x1_supported` and `ops.gconv1x1_wgrad_supported`."""
+
+    @staticmethod
+    def forward(ctx, x, bank, bias, res=None):
+        x = x.contiguous(memory_format=torch.channels_last)
+        ctx.save_for_backward(x, bank)
+        return ops.gconv1x1_nhwc(x, ops.pack_gconv1x1_weights(bank.detach()), bias.detach().contiguous(),
+                                 None if res is None else res.contiguous(memory_format=torch.channels_last))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, bank = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        cout, cin = bank.shape[:2]
+        dx = dbank = dbias = None
+        if ctx.needs_input_grad[0]:
+            wt = ops.pack_gconv1x1_weights(bank.detach().reshape(cout, cin).t().contiguous())
+            dx = ops.gconv1x1_nhwc(dy, wt, dy.new_zeros(cin))
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dbank, dbias = ops.gconv1x1_wgrad(x, dy)
+            dbank = dbank.reshape(bank.shape)
+        return (dx, dbank if ctx.needs_input_grad[1] else None, dbias if ctx.needs_input_grad[2] else None,
+                dy if len(ctx.needs_input_grad) > 3 and ctx.needs_input_grad[3] else None)
 
 
 class _ExactQuarterTurns:
@@ -344,10 +391,144 @@ class ESCNNWRNEquivariantNetwork(nn.Module):
         y = F.conv2d(h, bank, bias)
         return group_pool(y.reshape(y.shape[0], tail.out_channels, self.num_group_elements, y.shape[-2], y.shape[-1]))
 
+    # -- training route --------------------------------------------------------------------------------------------------------
+    def _train_ok(self, x: torch.Tensor) -> bool:
+        """The entry rule of `_forward_training`, from shapes and flags alone: training mode or gradients enabled, EQA_WRN_KERNEL != 0,
+        fp32 input and weights on the device, stride 1 and channel counts on the multiples of 4 everywhere, and at least one
+        bottleneck 1 x 1 layer that both eqa_gconv1x1_nhwc and eqa_gconv1x1_wgrad take at this input."""
+        if not (self.training or torch.is_grad_enabled()) or os.environ.get("EQA_WRN_KERNEL", "1") == "0":
+            return False
+        w = self.eqv_network[0].weights
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and w.is_cuda and w.dtype == torch.float32):
+            return False
+        E = self.num_group_elements
+        convs = [m for m in self.modules() if _is_conv(m)]
+        if any(c.stride != 1 or (c.out_channels * E) % 4 for c in convs):
+            return False
+        mods = list(self.eqv_network)
+        B, (H, W) = x.shape[0], x.shape[-2:]
+        H, W = (v + 2 * mods[0].padding - mods[0].kernel_size + 1 for v in (H, W))
+        admitted = False
+        for block in mods[3:-1:3]:
+            if min(H, W) < 1:
+                return False
+            if isinstance(block, ESCNNWideBottleneck):
+                for c in (block.conv_network[0], block.conv_network[6]):
+                    sizes = (B * H * W, c.in_channels * E, c.out_channels * E)
+                    admitted = admitted or (ops.gconv1x1_supported(*sizes) and ops.gconv1x1_wgrad_supported(*sizes))
+            else:
+                H, W = H - 2 * (block.kernel_size - 1), W - 2 * (block.kernel_size - 1)
+        return admitted and min(H, W) >= 1
+
+    def _forward_training(self, x: torch.Tensor, routes: List[str]) -> torch.Tensor:
+        """Same layers as ``self.eqv_network`` + group pooling with autograd, channels-last (B, fields * |G|, H, W) throughout.  Per
+        layer, from shapes alone: a 1 x 1 layer on `GConv1x1Function` ("gconv1x1"; a bottleneck's second one with the block input as
+        the residual, "gconv1x1+junction") where both kernels take it; a k x k layer, zero-padded by F.pad where the layer is
+        padded, on ``winograd.Conv5x5Function`` ("wino") or ``fftconv.ConvKxKFunction`` ("fftk") where their rules admit the map;
+        the stem on `LiftConvFunction` ("lift" / "lift_wide"); else the library's convolution ("lib").  Every InnerBatchNorm + ReLU
+        is one `InnerBnReluDropout` with p = 0 (batch statistics and the running-statistics update in training mode, running
+        statistics in eval mode; EQA_TRAIN_FUSED_BN=0: op by op).  A k x k layer's bias goes to the batch-norm behind it, where it
+        only shifts the mean.  The last convolution + group mean are window sums + a GEMV ("window_sums") where the tail is linear
+        and the map fits, else convolution + group_pool ("lib")."""
+        mods = list(self.eqv_network)
+        stem, tail = mods[0], mods[-1]
+        E = self.num_group_elements
+        fused_bn = os.environ.get("EQA_TRAIN_FUSED_BN", "1") != "0"
+        nhwc = torch.channels_last
+        handed: List[torch.Tensor] = []      # biases handed to a batch-norm: kept in the graph (see the end)
+
+        def bn_relu(h, bn, conv_bias):
+            if conv_bias is not None:
+                handed.append(conv_bias.sum())
+            if fused_bn and h.is_contiguous(memory_format=nhwc):
+                return InnerBnReluDropout.apply(h, bn.weight, bn.bias, bn, E, conv_bias, 0.0, False, None)
+            return torch.relu(ESCNNEquivariantNetwork._inner_bn(h, bn, E, conv_bias))
+
+        def one_by_one(h, conv, res):
+            bank = conv.expanded_weights()
+            cout, cin = bank.shape[:2]
+            bias = bank.new_zeros(cout) if conv.bias is None else conv.bias.repeat_interleave(E)
+            sizes = (h.shape[0] * h.shape[2] * h.shape[3], cin, cout)
+            if ops.gconv1x1_supported(*sizes) and ops.gconv1x1_wgrad_supported(*sizes):
+                routes.append("gconv1x1" if res is None else "gconv1x1+junction")
+                return GConv1x1Function.apply(h, bank, bias, res)
+            routes.append("lib")
+            y = F.conv2d(h, bank.contiguous(memory_format=nhwc), bias)
+            return y if res is None else y + res
+
+        def k_by_k(h, conv):                 # without the layer's bias
+            bank = conv.expanded_weights()
+            cout, cin = bank.shape[:2]
+            k, pad = conv.kernel_size, conv.padding
+            hp = (F.pad(h, (pad, pad, pad, pad)) if pad else h).contiguous(memory_format=nhwc)
+            if k == 5 and winograd.applicable(hp, cin, cout):
+                routes.append("wino")
+                return winograd.Conv5x5Function.apply(hp, bank, winograd.tile_for(hp), False)
+            if k != 5 and fftconv.applicable_k(hp.shape, cin, cout, k, hp.device):
+                routes.append("fftk")
+                return fftconv.ConvKxKFunction.apply(hp, bank)
+            routes.append("lib")
+            return F.conv2d(hp, bank.contiguous(memory_format=nhwc))
+
+        h = x.contiguous(memory_format=nhwc)
+        bank = stem.expanded_weights()
+        lift = ESCNNEquivariantNetwork._lift_kernel(stem, bank, h)
+        if lift is not None:
+            routes.append("lift" if lift == "narrow" else "lift_wide")
+            h = LiftConvFunction.apply(h, bank, False)
+        else:
+            routes.append("lib")
+            h = F.conv2d(h, bank.contiguous(memory_format=nhwc), padding=stem.padding)
+        h = bn_relu(h, mods[1], stem.bias)
+        for i in range(3, len(mods) - 1, 3):                      # (block, InnerBatchNorm, ReLU)
+            block, outer = mods[i], mods[i + 1]
+            if isinstance(block, ESCNNWideBottleneck):
+                c1, bn1, _, c2, bn2, _, c3 = block.conv_network
+                u = bn_relu(one_by_one(h, c1, None), bn1, None)
+                u = bn_relu(k_by_k(u, c2), bn2, c2.bias)
+                h = bn_relu(one_by_one(u, c3, h), outer, None)
+            else:
+                c1, bn1, _, c2 = block.conv_network
+                a = k_by_k(bn_relu(k_by_k(h, c1), bn1, c1.bias), c2)
+                bias = c2.bias
+                if block.shortcut is not None:
+                    sc = block.shortcut[0]
+                    a = a + k_by_k(h, sc)
+                    bias = sc.bias if bias is None else bias if sc.bias is None else bias + sc.bias
+                else:
+                    a = a + h
+                h = bn_relu(a, outer, bias)
+        k, O = tail.kernel_size, tail.out_channels
+        Bn, _, H, W = h.shape
+        bank = tail.expanded_weights()
+        if tail.supports_linear_tail() and min(H, W) >= 2 * k - 1 and H * W <= 12288 and Bn <= 65535:
+            routes.append("window_sums")
+            S = WindowSumsFunction.apply(h.contiguous(memory_format=nhwc), k)                      # (B, C, k, k) fp64
+            weff = bank.reshape(O, E, -1).double().sum(0)                                          # (E, C*k*k), differentiable
+            scale = 1.0 / float(O * (H - k + 1) * (W - k + 1))
+            if E <= 16 and os.environ.get("EQA_WS_TABLE_KERNEL", "1") != "0":
+                act = WindowSumsLinearFn.apply(S.flatten(1), weff, scale)
+            else:
+                act = S.flatten(1) @ weff.t() * scale
+            if tail.bias is not None:
+                act = act + tail.bias.double().mean()
+        else:
+            routes.append("lib")
+            y = F.conv2d(h, bank.contiguous(memory_format=nhwc), None if tail.bias is None else tail.bias.repeat_interleave(E),
+                         padding=tail.padding)
+            act = group_pool(y.reshape(Bn, O, E, y.shape[-2], y.shape[-1]).contiguous())
+        # a bias in front of a batch-norm with batch statistics cancels (zero gradient): it stays in the graph with that exact zero,
+        # so that every parameter has a gradient tensor and DistributedDataParallel counts it as used
+        if handed:
+            act = act + 0.0 * torch.stack(handed).sum()
+        return act.float()
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         routes: List[str] = []
         if self._fused_ok(x):
             out = self._forward_fused(x, routes)
+        elif self._train_ok(x):
+            out = self._forward_training(x, routes)
         else:
             h = x
             for m in self.eqv_network:

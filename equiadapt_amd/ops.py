@@ -1434,3 +1434,45 @@ def gconv1x1_nhwc(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, res: O
                                    _stream())
     _lib.check(st, "eqa_gconv1x1_nhwc")
     return y
+
+
+def gconv1x1_wgrad_supported(pixels: int, cin: int, cout: int) -> bool:
+    """Shapes and sizes eqa_gconv1x1_wgrad takes -- what `gconv1x1_supported` admits, the size test included."""
+    return bool(_lib.load().eqa_gconv1x1_wgrad_supported(pixels, cin, cout))
+
+
+def gconv1x1_wgrad(x: torch.Tensor, dz: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Filter and bias gradient of z = conv1x1(x) + bias for the output gradient dz (eqa_gconv1x1_wgrad: the contraction over the
+    pixels on the fp32 MFMA, split over the chip's waves, partial tiles added in a fixed order in fp64).  x, dz: channels-last
+    (B, C, H, W) maps or their (pixels, C) matrices, of the same number of pixels -> (dW (Cout, Cin, 1, 1), dbias (Cout,)).
+    No autograd."""
+    lib = _lib.load()
+    for t, name in ((x, "x"), (dz, "dz")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            raise RuntimeError(f"gconv1x1_wgrad expects fp32 tensors on the device ({name})")
+    if dz.device != x.device or dz.dim() != x.dim():
+        raise RuntimeError("gconv1x1_wgrad: x and dz must be on one device and of one layout")
+
+    def rows(t, name):
+        if t.dim() == 4:
+            if not t.is_contiguous(memory_format=torch.channels_last):
+                raise RuntimeError(f"gconv1x1_wgrad: {name} must be a channels-last map, got {tuple(t.shape)} with strides {t.stride()}")
+            return t.shape[0] * t.shape[2] * t.shape[3], t.shape[1]
+        if t.dim() != 2 or not t.is_contiguous():
+            raise RuntimeError(f"gconv1x1_wgrad: {name} must be a contiguous (pixels, channels) matrix, got {tuple(t.shape)}")
+        return t.shape[0], t.shape[1]
+
+    (P, Cin), (Pz, Cout) = rows(x, "x"), rows(dz, "dz")
+    if Pz != P:
+        raise ValueError(f"gconv1x1_wgrad: x has {P} pixels, dz {Pz}")
+    if not gconv1x1_wgrad_supported(P, Cin, Cout):
+        raise _lib.EqaLibraryError(f"eqa_gconv1x1_wgrad does not take {P} pixels of {Cin} -> {Cout} channels (ask gconv1x1_wgrad_supported first)")
+    dW = torch.empty((Cout, Cin, 1, 1), dtype=torch.float32, device=x.device)
+    dbias = torch.empty(Cout, dtype=torch.float32, device=x.device)
+    nbytes = lib.eqa_gconv1x1_wgrad_workspace_bytes(P, Cin, Cout)
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("gconv1x1_wgrad"):
+        st = lib.eqa_gconv1x1_wgrad(x.data_ptr(), dz.data_ptr(), dW.data_ptr(), dbias.data_ptr(), work.data_ptr() if nbytes else None,
+                                    P, Cin, Cout, _stream())
+    _lib.check(st, "eqa_gconv1x1_wgrad")
+    return dW, dbias

@@ -898,12 +898,29 @@ int eqa_vn_act_bwd(const float* x, const float* Wd, const float* gy, float* gx, 
  * eqa_gconv1x1_supported: Cin, Cout multiples of 32 in [32, 512], and P * max(Cin, Cout) * 4 bytes within one 32-bit buffer
  * range (<= 0xffffff00) -- the size test is part of the query, so a caller that asks first never meets EQA_ERR_UNSUPPORTED from the
  * launch for a size.  Pointers 16-byte aligned (else EQA_ERR_UNSUPPORTED).  Rows >= P are never written.  P = 0: nothing is launched.
- * fmaf chains over c in a fixed order: two launches on the same input give the same bits.  No gradient.
+ * fmaf chains over c in a fixed order: two launches on the same input give the same bits.
  * Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ *
+ * Gradients.  dx = dz W^T is eqa_gconv1x1_nhwc itself on the packed transpose of W (zero bias, nothing else).  The filter and bias
+ * gradient, a contraction over the pixels on the same matrix instruction:
+ *   dW[o][c] = sum_p x[p][c] dz[p][o]   (Cout, Cin): the layout of the convolution's (Cout, Cin, 1, 1) filters
+ *   dbias[o] = sum_p dz[p][o]
+ * x:(P,Cin), dz:(P,Cout).  eqa_gconv1x1_wgrad_supported admits what eqa_gconv1x1_supported admits (the size test included).  The
+ * pixel range is split over the chip's waves; every wave writes a partial tile to workspace (eqa_gconv1x1_wgrad_workspace_bytes
+ * bytes, a function of the sizes alone; 0 for P = 0 and for sizes the query refuses) and a second launch adds the partials in a
+ * fixed order in fp64: no atomics, two calls on the same operands give the same bits.  Nothing past row P - 1 of x or dz is read.
+ * P = 0: nothing is launched, dW and dbias are zeroed (workspace may be NULL).  A refused size: EQA_ERR_UNSUPPORTED before any
+ * pointer is looked at.  NULL pointers, outputs or workspace aliasing an operand or each other: EQA_ERR_INVALID_ARG (equal base
+ * pointers are detected; buffers that overlap otherwise are the caller's error and are not).  Pointers not 16-byte aligned:
+ * EQA_ERR_UNSUPPORTED.
  */
 int eqa_gconv1x1_supported(long long P, int Cin, int Cout);
 int eqa_gconv1x1_nhwc(const float* x, const float* Wpk, const float* bias, const float* res, const float* s, const float* t, int relu,
                       float* y, long long P, int Cin, int Cout, void* stream);
+int eqa_gconv1x1_wgrad_supported(long long P, int Cin, int Cout);
+long long eqa_gconv1x1_wgrad_workspace_bytes(long long P, int Cin, int Cout);
+int eqa_gconv1x1_wgrad(const float* x, const float* dz, float* dW, float* dbias, void* workspace, long long P, int Cin, int Cout,
+                       void* stream);
 
 #ifdef __cplusplus
 }

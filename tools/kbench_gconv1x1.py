@@ -8,6 +8,9 @@ device events after a warm-up, median over the rounds:
              where the kernel does not take a shape (F.conv2d with bias, add_, mul_, add_, relu_), and against a clone() that moves
              the same bytes (the junction reads u and h and writes y: three maps; the clone reads and writes 1.5 maps)
   network    the whole recipe network in eval under no_grad, fused route against plain route (EQA_WRN_KERNEL=0)
+  wgrad      the filter and bias gradient of the 1 x 1 convolution at the same maps: eqa_gconv1x1_wgrad against dz.t() @ x on the
+             library GEMM
+  train_step one forward + backward of the recipe network in train(): training route against plain route (EQA_WRN_KERNEL=0)
 One JSON line per (shape, leg).  --small: tiny shapes and few calls, to rehearse."""
 import json
 import os
@@ -97,3 +100,49 @@ with torch.no_grad():
                       "speedup": med["plain"] / med["fused"], "max_abs_diff_of_outputs": diff, "max_abs_output": float(b.abs().max()),
                       "min_max_ms": spread, "routes": routes}), flush=True)
 os.environ.pop(ENV, None)
+
+
+def train_legs():
+    """wgrad: eqa_gconv1x1_wgrad (filter and bias gradient, two launches) against dz.t() @ x on the library GEMM (which leaves the
+    bias gradient out) at the same three maps.  train_step: forward + backward of the recipe network in train(), the training route
+    against the plain route (EQA_WRN_KERNEL=0)."""
+    for shape in SHAPES:
+        torch.manual_seed(0)
+        B, C, H, W = shape
+        P = B * H * W
+        x, dz = torch.randn(P, C, device=dev), torch.randn(P, C, device=dev)
+        assert ops.gconv1x1_wgrad_supported(P, C, C)
+        ref = dz.double().t() @ x.double()
+        err_k = float((ops.gconv1x1_wgrad(x, dz)[0].view(C, C).double() - ref).abs().max())
+        err_l = float(((dz.t() @ x).double() - ref).abs().max())
+        med, spread = alternate({"kernel": lambda: ops.gconv1x1_wgrad(x, dz), "library_gemm": lambda: dz.t() @ x}, N, ROUNDS)
+        print(json.dumps({"shape": shape, "leg": "wgrad", "kernel_ms": med["kernel"], "library_gemm_ms": med["library_gemm"],
+                          "speedup_over_library_gemm": med["library_gemm"] / med["kernel"],
+                          "kernel_TFLOP_per_s": 2 * P * C * C / (med["kernel"] * 1e-3) / 1e12,
+                          "kernel_TB_per_s": 2 * P * C * 4 / (med["kernel"] * 1e-3) / 1e12,
+                          "max_abs_err_to_fp64": {"kernel": err_k, "library_gemm": err_l}, "min_max_ms": spread}), flush=True)
+        del x, dz, ref
+
+    torch.manual_seed(0)
+    cfg = ((3, 40, 40), 32, 5, "rotation", 6, 4) if small else ((3, 128, 128), 64, 5, "rotation", 12, 4)
+    net = ea.ESCNNWRNEquivariantNetwork(*cfg).to(dev).train()
+    x = torch.randn(2 if small else 8, *cfg[0], device=dev)
+    routes = {}
+
+    def step(fused):
+        os.environ[ENV] = "1" if fused else "0"
+        net.zero_grad(set_to_none=True)
+        y = net(x)
+        routes["train" if fused else "plain"] = list(net.last_routes)
+        y.square().sum().backward()
+        return y.detach()
+
+    a, b = step(True), step(False)
+    med, spread = alternate({"train": lambda: step(True), "plain": lambda: step(False)}, max(N // 4, 2), ROUNDS)
+    print(json.dumps({"config": cfg, "batch": x.shape[0], "leg": "train_step", "train_route_ms": med["train"], "plain_ms": med["plain"],
+                      "speedup": med["plain"] / med["train"], "max_abs_diff_of_outputs": float((a - b).abs().max()),
+                      "max_abs_output": float(b.abs().max()), "min_max_ms": spread, "routes": routes}), flush=True)
+    os.environ.pop(ENV, None)
+
+
+train_legs()

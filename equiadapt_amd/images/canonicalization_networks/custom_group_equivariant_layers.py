@@ -10,13 +10,14 @@ bit-compatible with what the kernel (hence the reference op sequence) produces.
 Parameter names/shapes (``weights``, ``bias``) match the reference so its checkpoints load.
 """
 import math
-from typing import Dict, Tuple
+from typing import Dict
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from equiadapt_amd import ops
+from equiadapt_amd.common.derived import DerivedCache
 from equiadapt_amd.images import geometry
 
 _bank_cache: Dict[tuple, torch.Tensor] = {}
@@ -91,47 +92,38 @@ class _GroupConvBase(nn.Module):
         self.num_group_elements = E
         if not self.lifting:
             self.register_buffer("src_slot", _slot_table(num_rotations, self.reflections), persistent=False)
-        self._cached_bank: Tuple[int, torch.Tensor] = (-1, None)  # type: ignore
+        self._cache = DerivedCache()
+
+    def _action_matrices(self, w: torch.Tensor) -> torch.Tensor:
+        return filter_action_matrices(self.kernel_size, self.num_rotations, self.reflections, w.device).to(w.dtype)  # (E, p, q)
+
+    def _expand(self) -> torch.Tensor:
+        w = self.weights
+        O, I, E, k = self.out_channels, self.in_channels, self.num_group_elements, self.kernel_size
+        A = self._action_matrices(w)
+        if self.lifting:
+            return torch.einsum("epq,oiq->oeip", A, w.reshape(O, I, k * k)).reshape(O * E, I, k, k)
+        wp = w.reshape(O, I, E, k * k)[:, :, self.src_slot]            # (O, I, E[e], E[m], q)
+        return torch.einsum("epq,oiemq->oeimp", A, wp).reshape(O * E, I * E, k, k)
 
     def expanded_weights(self) -> torch.Tensor:
-        """The dense conv filter bank: (O*E, I, k, k) for lifting, (O*E, I*E, k, k) otherwise."""
-        w = self.weights
-        if not self.training and not torch.is_grad_enabled():
-            ver, bank = self._cached_bank
-            if ver == w._version and bank is not None and bank.device == w.device:
-                return bank
-        O, I, E, k = self.out_channels, self.in_channels, self.num_group_elements, self.kernel_size
-        A = filter_action_matrices(k, self.num_rotations, self.reflections, w.device).to(w.dtype)  # (E, p, q)
-        if self.lifting:
-            bank = torch.einsum("epq,oiq->oeip", A, w.reshape(O, I, k * k)).reshape(O * E, I, k, k)
-        else:
-            wp = w.reshape(O, I, E, k * k)[:, :, self.src_slot]            # (O, I, E[e], E[m], q)
-            bank = torch.einsum("epq,oiemq->oeimp", A, wp).reshape(O * E, I * E, k, k)
-        if not self.training and not torch.is_grad_enabled():
-            self._cached_bank = (w._version, bank)
-        return bank
+        """The dense conv filter bank: (O*E, I, k, k) for lifting, (O*E, I*E, k, k) otherwise.  Kept in eval mode without autograd."""
+        if self.training or torch.is_grad_enabled():
+            return self._expand()
+        return self._cache.get("bank", (self.weights,), self._expand)
 
     def mean_response_weights(self) -> torch.Tensor:
         """(E, Cin*k*k) fp64: the expanded bank summed over output fields (see pooling.conv_then_group_pool)."""
-        w = self.weights
-        ver, hit = getattr(self, "_cached_weff", (-1, None))
-        if ver == w._version and hit is not None and hit.device == w.device:
-            return hit
-        bank = self.expanded_weights().detach()
-        weff = bank.view(self.out_channels, self.num_group_elements, -1).double().sum(0)
-        self._cached_weff = (w._version, weff)
-        return weff
+        return self._cache.get("weff", (self.weights,), lambda: self.expanded_weights().detach().view(
+            self.out_channels, self.num_group_elements, -1).double().sum(0))
 
     def mean_bias_value(self) -> float:
-        """mean(bias) as a Python float, cached per parameter version (inference: one host read when the weights change,
-        then no launches at all for the bias of the linearised last layer)."""
-        if self.bias is None:
+        """mean(bias) as a Python float (inference: one host read when the bias changes, then no launches at all for the bias of the
+        linearised last layer)."""
+        b = self.bias
+        if b is None:
             return 0.0
-        ver, hit = getattr(self, "_cached_bias_mean", (-1, 0.0))
-        if ver != self.bias._version:
-            hit = float(self.bias.detach().double().mean().item())
-            self._cached_bias_mean = (self.bias._version, hit)
-        return hit
+        return self._cache.get("bias_mean", (b,), lambda: float(b.detach().double().mean().item()))
 
     def supports_linear_tail(self) -> bool:
         return self.stride == 1 and self.padding == 0 and self.kernel_size <= ops.MAX_WINDOW_K
@@ -148,17 +140,16 @@ class _GroupConvBase(nn.Module):
     def lift_nhwc(self, x: torch.Tensor, relu: bool = False) -> torch.Tensor:
         """[relu](lifting convolution + bias) as a channels-last (B, O*|G|, H', W') tensor (channel = field * |G| + element): the
         layout the window-sum kernels read, without the 5-D reshape of ``forward``."""
-        w, b = self.weights, self.bias
-        key = (w._version, -1 if b is None else b._version, str(w.device))
-        hit = getattr(self, "_cached_lift", None)
-        if hit is None or hit[0] != key:
+        b = self.bias
+
+        def build():
             narrow = ops.lift_conv_supported(self.in_channels, self.kernel_size, self.kernel_size, self.out_channels * self.num_group_elements)
             wpk = (ops.pack_lift_weights if narrow else ops.pack_lift_weights_wide)(self.expanded_weights().detach())
-            be = None if b is None else b.detach().repeat_interleave(self.num_group_elements).contiguous()
-            hit = (key, wpk, be, narrow)
-            self._cached_lift = hit
-        fn = ops.lift_conv_nhwc if hit[3] else ops.lift_conv_wide
-        return fn(x.contiguous(memory_format=torch.channels_last), hit[1], hit[2], relu, self.kernel_size, self.kernel_size)
+            return wpk, None if b is None else b.detach().repeat_interleave(self.num_group_elements).contiguous(), narrow
+
+        wpk, be, narrow = self._cache.get("lift", (self.weights, b), build)
+        fn = ops.lift_conv_nhwc if narrow else ops.lift_conv_wide
+        return fn(x.contiguous(memory_format=torch.channels_last), wpk, be, relu, self.kernel_size, self.kernel_size)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         B = x.shape[0]

@@ -11,6 +11,8 @@ from typing import List
 import torch
 from torch import nn
 
+from equiadapt_amd.common.derived import DerivedCache, bn_eval_affine
+
 
 _BN_FLAG_LOCK = threading.Lock()
 
@@ -104,41 +106,42 @@ class ConvNetwork(nn.Module):
         self.final_fc = nn.Sequential(nn.BatchNorm1d(out_dim), nn.Dropout1d(0.5), nn.ReLU(),
                                       nn.Linear(out_dim, out_vector_size))
         self.out_vector_size = out_vector_size
-        self._fold_cache: dict = {}
+        self._cache = DerivedCache()
 
     def _folded(self, conv: nn.Conv2d, bn: nn.BatchNorm2d):
-        """Weights and bias of ``bn(conv(.))`` in eval mode (one convolution, no separate normalisation pass); cached per
-        parameter version."""
-        key = (conv.weight._version, None if conv.bias is None else conv.bias._version, bn.weight._version, bn.bias._version,
-               bn.running_mean._version, bn.running_var._version, str(conv.weight.device))
-        hit = self._fold_cache.get(id(conv))
-        if hit is None or hit[0] != key:
+        """Weights and bias of ``bn(conv(.))`` in eval mode (one convolution, no separate normalisation pass)."""
+        def build():
             scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
             bias = conv.bias if conv.bias is not None else torch.zeros_like(scale)
-            hit = (key, (conv.weight * scale[:, None, None, None]).contiguous(), ((bias - bn.running_mean) * scale + bn.bias).contiguous())
-            self._fold_cache[id(conv)] = hit
-        return hit[1], hit[2]
+            return (conv.weight * scale[:, None, None, None]).contiguous(), ((bias - bn.running_mean) * scale + bn.bias).contiguous()
+
+        return self._cache.get(conv, (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
+
+    def _plan_sources(self) -> list:
+        """Every tensor `_mfma_plan` reads, straight from the modules' own tables: walking parameters() / buffers() costs ~20 us per
+        forward, a tenth of a configs[4] step at B = 4."""
+        mods = tuple(self.enc_network._modules.values())
+        fc = self.final_fc._modules
+        p, b = fc["0"]._parameters, fc["0"]._buffers
+        src = [p["weight"], p["bias"], b["running_mean"], b["running_var"], fc["3"]._parameters["weight"]]
+        for i in range(0, len(mods), 3):                           # (convolution, batch-norm, GELU)
+            c, p, b = mods[i]._parameters, mods[i + 1]._parameters, mods[i + 1]._buffers
+            src += (c["weight"], c["bias"], p["weight"], p["bias"], b["running_mean"], b["running_var"])
+        return src
 
     def _mfma_plan(self, x: torch.Tensor):
         """Per layer (packed weights, bias, Cout, k, pad, planar) when EVERY convolution of the encoder fits eqa_conv_s2 (stride 2,
         k in {3,5,7}, first layer <= 4 input planes, then multiples of 16 channels), plus the head's parameters re-indexed from
-        the reference's (C,H,W) flattening to the kernels' channels-last one; None otherwise.  Cached per parameter version."""
+        the reference's (C,H,W) flattening to the kernels' channels-last one; None otherwise."""
+        return self._cache.get("mfma", self._plan_sources(), lambda: self._build_mfma_plan(x), x.shape[1:], x.device)
+
+    def _build_mfma_plan(self, x: torch.Tensor):
         from equiadapt_amd import ops
 
-        # fast path of the cache: the tensor OBJECTS the plan was built from (walking the modules' parameters / buffers costs ~20 us per
-        # forward, a tenth of a configs[4] step at B = 4), valid while the module tree still holds exactly those objects
-        hit = self._fold_cache.get("mfma")
-        if hit is not None:
-            tensors = hit[2]
-            if (hit[0] == tuple(t._version for t in tensors) + (tuple(x.shape[1:]), x.device)
-                    and all(a is b for a, b in zip(hit[3], self._plan_objects()))):
-                return hit[1]
         mods = list(self.enc_network)
         convs, bns = mods[0::3], mods[1::3]
         if any(not isinstance(a, nn.GELU) or a.approximate != "none" for a in mods[2::3]) or any(bn.running_mean is None for bn in bns):
             return None
-        tensors = [t for m in list(convs) + list(bns) + [self.final_fc[0], self.final_fc[3]] for t in list(m.parameters()) + list(m.buffers())]
-        key = tuple(t._version for t in tensors) + (tuple(x.shape[1:]), x.device)
         plan, layers, hw = None, [], tuple(x.shape[-2:])
         ok = True
         per_sample = [x.shape[1] * hw[0] * hw[1] * 4]      # bytes of every activation per sample (eqa_conv_s2 addresses < 2^31 bytes)
@@ -157,23 +160,13 @@ class ConvNetwork(nn.Module):
             C = convs[-1].out_channels
             # feature d of the reference = c * H * W + y * W + x; the kernels produce (y, x, c): gather the head's parameters
             idx = torch.arange(C * hw[0] * hw[1], device=x.device).view(C, hw[0], hw[1]).permute(1, 2, 0).reshape(-1)
-            scale = bn1.weight / torch.sqrt(bn1.running_var + bn1.eps)
-            shift = bn1.bias - bn1.running_mean * scale
+            scale, shift = bn_eval_affine(bn1)
             # largest batch one eqa_conv_s2 call takes (every activation below 2^31 bytes); larger batches run in chunks, which
             # needs every per-sample activation to be a multiple of 16 bytes (the kernels' 16-byte loads start at the chunk's base)
             max_batch = (2 ** 31 - 64) // max(per_sample)
             chunkable = all(b % 16 == 0 for b in per_sample)
             plan = (layers, scale[idx].contiguous(), shift[idx].contiguous(), lin.weight[:, idx].contiguous(), max_batch, chunkable)
-        self._fold_cache["mfma"] = (key, plan, tensors, self._plan_objects())
         return plan
-
-    def _plan_objects(self):
-        """The tensors whose REPLACEMENT (not in-place update: that bumps ._version) must invalidate the cached plan: every
-        convolution's weight, every batch-norm's running mean (tests and checkpoint loaders assign those), the head's weight."""
-        enc = self.enc_network._modules
-        objs = [m._parameters["weight"] if i % 3 == 0 else m._buffers["running_mean"] for i, m in enumerate(enc.values()) if i % 3 != 2]
-        fc = self.final_fc._modules
-        return objs + [fc["0"]._buffers["running_mean"], fc["3"]._parameters["weight"]]
 
     def _train_hip_applies(self, x: torch.Tensor) -> bool:
         """Training / autograd forward on the library's own kernels: every layer Conv2d(stride 2, k in 3/5/7, padding 0/1) over
@@ -274,13 +267,9 @@ class ConvNetwork(nn.Module):
                 # head: BatchNorm1d (eval, folded) + [Dropout1d: identity] + ReLU in one pass, then the Linear layer
                 from equiadapt_amd import ops
 
-                key = (bn1.weight._version, bn1.bias._version, bn1.running_mean._version, bn1.running_var._version, str(h.device))
-                hit = self._fold_cache.get("head")
-                if hit is None or hit[0] != key:
-                    scale = (bn1.weight / torch.sqrt(bn1.running_var + bn1.eps)).contiguous()
-                    hit = (key, scale, (bn1.bias - bn1.running_mean * scale).contiguous())
-                    self._fold_cache["head"] = hit
-                return torch.nn.functional.linear(ops.affine_relu_rows(h.contiguous(), hit[1], hit[2]), lin.weight, lin.bias)
+                scale, shift = self._cache.get("head", (bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var),
+                                               lambda: tuple(t.contiguous() for t in bn_eval_affine(bn1)))
+                return torch.nn.functional.linear(ops.affine_relu_rows(h.contiguous(), scale, shift), lin.weight, lin.bias)
             return self.final_fc(h)
         mode = os.environ.get("EQA_CONVNET_TRAIN_MODE", "hip")
         if mode == "hip" and self._train_hip_applies(x):

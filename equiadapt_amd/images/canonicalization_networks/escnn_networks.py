@@ -26,6 +26,7 @@ from equiadapt_amd.images.canonicalization_networks.custom_group_equivariant_lay
     RotoReflectionEquivariantConvLift,
 )
 from equiadapt_amd import ops
+from equiadapt_amd.common.derived import DerivedCache, bn_eval_affine, refuse_e2cnn_state_dict
 from equiadapt_amd.common.utils import update_running_stats
 from equiadapt_amd.images.canonicalization_networks import fftconv, winograd
 from equiadapt_amd.images.canonicalization_networks.pooling import (
@@ -212,6 +213,7 @@ class _DenseConv(nn.Module):
         self.lifting = lifting
         self.kernel_size, self.stride, self.padding = conv.kernel_size[0], conv.stride[0], conv.padding[0]
         self.out_channels = conv.out_channels // num_group_elements          # fields, like the group convolutions
+        self._cache = DerivedCache()
 
     @property
     def weights(self):
@@ -226,11 +228,7 @@ class _DenseConv(nn.Module):
 
     def mean_response_weights(self) -> torch.Tensor:
         w = self.conv.weight
-        ver, hit = getattr(self, "_cached_weff", (-1, None))
-        if ver != w._version or hit is None or hit.device != w.device:
-            hit = w.detach().view(self.out_channels, self.num_group_elements, -1).double().sum(0)
-            self._cached_weff = (w._version, hit)
-        return hit
+        return self._cache.get("weff", (w,), lambda: w.detach().view(self.out_channels, self.num_group_elements, -1).double().sum(0))
 
     def mean_bias_value(self):
         """Per-ELEMENT mean of the bias over the fields, (|G|,) fp64: an exported bias is constant within a regular field for an
@@ -238,12 +236,12 @@ class _DenseConv(nn.Module):
         b = self.conv.bias
         if b is None:
             return 0.0
-        ver, hit = getattr(self, "_cached_bias_mean", (-1, None))
-        if ver != b._version or hit is None:
+
+        def build():
             m = b.detach().double().view(self.out_channels, self.num_group_elements).mean(0)
-            hit = float(m[0].item()) if bool((m == m[0]).all().item()) else m
-            self._cached_bias_mean = (b._version, hit)
-        return hit
+            return float(m[0].item()) if bool((m == m[0]).all().item()) else m
+
+        return self._cache.get("bias_mean", (b,), build)
 
     def supports_linear_tail(self) -> bool:
         return self.stride == 1 and self.padding == 0 and self.kernel_size <= ops.MAX_WINDOW_K
@@ -281,21 +279,17 @@ class ESCNNEquivariantNetwork(nn.Module):
         mods.append(conv(out_channels, out_channels, kernel_size, num_rotations, device="cpu"))
         self.eqv_network = nn.Sequential(*mods)
         self._dense: Sequence = ()
-        self._fold_cache: dict = {}
+        self._cache = DerivedCache()
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         """A checkpoint of the reference's e2cnn network (escnn_networks.py:48-91) cannot be loaded by key: e2cnn stores a flat
         coefficient vector per layer over its steerable basis (``...weights`` 1-D, ``...basisexpansion...`` / ``...filter``
         buffers), this network stores rotated filter banks.  Say so instead of failing on a shape mismatch."""
-        own = prefix + "eqv_network."
-        for k, v in state_dict.items():
-            if k.startswith(own) and ("basisexpansion" in k or k.endswith(".filter") or k.endswith(".expanded_bias")
-                                      or (k.endswith(".weights") and getattr(v, "dim", lambda: 2)() == 1)):
-                raise RuntimeError(
-                    f"state_dict key {k!r} comes from e2cnn's steerable-basis parameterisation (the reference's ESCNNEquivariantNetwork). "
-                    "equiadapt_amd.ESCNNEquivariantNetwork parameterises its layers by rotated filter banks and cannot load it by key; "
-                    "export the trained layers on the e2cnn side (R2Conv.export() -> nn.Conv2d, InnerBatchNorm.export() -> nn.BatchNorm2d) "
-                    "and pass them to load_exported_dense(convs, norms).")
+        refuse_e2cnn_state_dict(
+            state_dict, prefix + "eqv_network.", "ESCNNEquivariantNetwork",
+            "equiadapt_amd.ESCNNEquivariantNetwork parameterises its layers by rotated filter banks and cannot load it by key; "
+            "export the trained layers on the e2cnn side (R2Conv.export() -> nn.Conv2d, InnerBatchNorm.export() -> nn.BatchNorm2d) "
+            "and pass them to load_exported_dense(convs, norms).", (".expanded_bias",))
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def load_exported_dense(self, convs: Sequence[nn.Conv2d], norms: Sequence[nn.BatchNorm2d]) -> None:
@@ -317,7 +311,7 @@ class ESCNNEquivariantNetwork(nn.Module):
             if bn.num_features != convs[i].out_channels:
                 raise ValueError(f"exported norm {i} has {bn.num_features} features, conv {i} produces {convs[i].out_channels}")
         self._dense = (nn.ModuleList(_DenseConv(cv, E, i == 0) for i, cv in enumerate(convs)), nn.ModuleList(norms))
-        self._fold_cache.clear()
+        self._cache.clear()
 
     def export_dense(self):
         """(convs, norms): this network's layers in the exported dense form -- expanded filter banks as ``nn.Conv2d`` (bias per
@@ -352,35 +346,21 @@ class ESCNNEquivariantNetwork(nn.Module):
     # -- inference fast path ------------------------------------------------------------------------------------
     def _folded(self, conv, bn):
         """Filter bank and bias of ``bn(conv(.))`` in eval mode: the per-field affine of the batch-norm is folded into
-        the bank (one conv, no separate bias / normalisation passes over the feature map).  Cached per weight version."""
-        key = (conv.weights._version, bn.weight._version, bn.bias._version, bn.running_mean._version,
-               bn.running_var._version, str(conv.weights.device))
-        hit = self._fold_cache.get(id(conv))
-        if hit is not None and hit[0] == key:
-            return hit[1], hit[2]
-        E = conv.num_group_elements
-        scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)                    # per field (per channel: exported form)
-        shift = bn.bias - bn.running_mean * scale
-        b = conv.bias if conv.bias is not None else torch.zeros_like(scale)
-        bias = b * scale + shift
-        if not isinstance(conv, _DenseConv):
-            scale, bias = scale.repeat_interleave(E), bias.repeat_interleave(E)
-        bank = conv.expanded_weights() * scale[:, None, None, None]
-        # channels-last: MIOpen's fp32 implicit-GEMM kernels are NHWC; keeping the bank (and the activations) in that
-        # layout removes the NCHW<->NHWC transposes around every convolution
-        bank, bias = bank.contiguous(memory_format=torch.channels_last), bias.contiguous()
-        self._fold_cache[id(conv)] = (key, bank, bias)
-        return bank, bias
+        the bank (one conv, no separate bias / normalisation passes over the feature map).  Cached under conv; what is built from
+        the bank (transformed filters, packed weights) is cached beside it under ``(conv, tag)``: ``self._cache.derived``."""
+        def build():
+            E = conv.num_group_elements
+            scale, shift = bn_eval_affine(bn)                                      # per field (per channel: exported form)
+            b = conv.bias if conv.bias is not None else torch.zeros_like(scale)
+            bias = b * scale + shift
+            if not isinstance(conv, _DenseConv):
+                scale, bias = scale.repeat_interleave(E), bias.repeat_interleave(E)
+            bank = conv.expanded_weights() * scale[:, None, None, None]
+            # channels-last: MIOpen's fp32 implicit-GEMM kernels are NHWC; keeping the bank (and the activations) in that
+            # layout removes the NCHW<->NHWC transposes around every convolution
+            return bank.contiguous(memory_format=torch.channels_last), bias.contiguous()
 
-    def _derived(self, conv, build, *tag):
-        """Something built from conv's folded bank (transformed filters, packed weights), cached under ``(*tag, id(conv))`` for as
-        long as `_folded`'s own entry for conv keeps its key."""
-        key = self._fold_cache[id(conv)][0]
-        hit = self._fold_cache.get((*tag, id(conv)))
-        if hit is None or hit[0] != key:
-            hit = (key, build())
-            self._fold_cache[(*tag, id(conv))] = hit
-        return hit[1]
+        return self._cache.get(conv, (conv.weights, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
 
     @staticmethod
     def _plain_5x5(conv) -> bool:
@@ -463,10 +443,10 @@ class ESCNNEquivariantNetwork(nn.Module):
                 in_bias, pending = pending, None
                 sums_k = tail.kernel_size if sums else 0
                 if route == "wino":
-                    U = self._derived(conv, lambda: winograd.transform_filters(bank, m), "wino", m)
+                    U = self._cache.derived(conv, (conv, "wino", m), lambda: winograd.transform_filters(bank, m))
                     h = winograd.conv5x5(h, U, bias, relu=True, in_bias=in_bias, in_relu=in_bias is not None, sums_k=sums_k)
                 else:
-                    Bf = self._derived(conv, lambda: fftconv.spectra_for_k(bank), "fft")
+                    Bf = self._cache.derived(conv, (conv, "fft"), lambda: fftconv.spectra_for_k(bank))
                     if route == "fft5":
                         h = fftconv.conv5x5(h, Bf, bias, True, in_bias, in_bias is not None, sums_k=sums_k)
                     else:
@@ -479,11 +459,11 @@ class ESCNNEquivariantNetwork(nn.Module):
                     operand = {}
                     form = fftconv.LiftedInput.form_operand()     # the kernel form's packed filters, cached per weight version
                     if form is not None:
-                        operand[form[1]] = self._derived(conv, lambda: form[2](bank), form[0])
+                        operand[form[1]] = self._cache.derived(conv, (conv, form[0]), lambda: form[2](bank))
                     h = fftconv.LiftedInput(h, bank, bias, True, **operand)
                 elif route != "lib":                                  # the unfused lifting kernels: bias + ReLU in their epilogues
                     pack = ops.pack_lift_weights_wide if route == "lift_wide" else ops.pack_lift_weights
-                    wpk = self._derived(conv, lambda: pack(bank), "lift")
+                    wpk = self._cache.derived(conv, (conv, "lift"), lambda: pack(bank))
                     if route == "lift_grouped":
                         h = fftconv.GroupedMap(ops.lift_conv_grouped(h, wpk, bias, True, k, k))
                     else:

@@ -30,6 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from equiadapt_amd import ops
+from equiadapt_amd.common.derived import DerivedCache, refuse_e2cnn_state_dict
 from equiadapt_amd.images.canonicalization_networks import fftconv
 from equiadapt_amd.images.canonicalization_networks.pooling import WindowSumsFunction
 
@@ -125,7 +126,7 @@ class SteerableConv(_Fp64Tables):
         J = kernel_size // 2 + 1
         M, N = len(_FREQS[out_kind]), len(_FREQS[in_kind])
         self.weights = nn.Parameter(torch.zeros(out_fields, in_fields, M, N, 2, J, 2))
-        self._cached_bank = self._cached_spectra = None          # eval: (key, dense bank) / (bank, its FFT spectra), see ESCNNSteerableNetwork
+        self._cache = DerivedCache()                             # eval: "bank", the dense bank, and "fft", its spectra: see ESCNNSteerableNetwork
         self.register_buffer("basis", steerable_basis(kernel_size).to(torch.get_default_dtype()))
         for name, table in self._tables().items():
             if name != "basis":
@@ -236,22 +237,20 @@ class FieldNorm(nn.Module):
         self.register_buffer("running_mean", torch.zeros(fields))
         self.register_buffer("running_var", torch.ones(fields, MAX_FREQ + 1))
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
-        self._folded: tuple = ()
+        self._cache = DerivedCache()
 
     def _scale_shift(self, mean: torch.Tensor, var: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         scale = self.weight * torch.rsqrt(var + self.eps)                     # (fields, 5)
         return scale, self.bias - mean * scale[:, 0]
 
     def folded(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(scale (fields, 5), shift (fields,)) of the eval-mode norm, what `ops.fourier_elu` applies on its loads.  Cached per
-        parameter / buffer version."""
-        key = (self.weight._version, self.bias._version, self.running_mean._version, self.running_var._version,
-               str(self.weight.device), self.weight.dtype)
-        if not self._folded or self._folded[0] != key:
+        """(scale (fields, 5), shift (fields,)) of the eval-mode norm, what `ops.fourier_elu` applies on its loads."""
+        def build():
             with torch.no_grad():
                 scale, shift = self._scale_shift(self.running_mean, self.running_var)
-            self._folded = (key, scale.contiguous(), shift.contiguous())
-        return self._folded[1], self._folded[2]
+            return scale.contiguous(), shift.contiguous()
+
+        return self._cache.get("folded", (self.weight, self.bias, self.running_mean, self.running_var), build)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         C = self.fields
@@ -343,27 +342,20 @@ class ESCNNSteerableNetwork(nn.Module):
         R2Conv over its own steerable basis (``...weights`` 1-D, ``...basisexpansion...`` / ``...filter`` buffers) and GNormBatchNorm
         statistics per irrep (``..._running_var`` / ``..._weight`` named after the irrep); this network's weights are complex
         ring / harmonic coefficients.  Say so instead of failing on a missing key or a shape mismatch."""
-        own = prefix + "block."
-        for k, v in state_dict.items():
-            if k.startswith(own) and ("basisexpansion" in k or k.endswith(".filter") or "irrep_" in k
-                                      or (k.endswith(".weights") and getattr(v, "dim", lambda: 7)() == 1)):
-                raise RuntimeError(
-                    f"state_dict key {k!r} comes from e2cnn's steerable-basis parameterisation (the reference's ESCNNSteerableNetwork). "
-                    "equiadapt_amd.ESCNNSteerableNetwork keeps the reference's constructor, layer order and output contract but "
-                    "parameterises its convolutions by complex ring / harmonic weights of its own and uses its own field norm: it is "
-                    "a different function class, e2cnn checkpoints cannot be loaded, and there is no bridge for them.")
+        refuse_e2cnn_state_dict(
+            state_dict, prefix + "block.", "ESCNNSteerableNetwork",
+            "equiadapt_amd.ESCNNSteerableNetwork keeps the reference's constructor, layer order and output contract but "
+            "parameterises its convolutions by complex ring / harmonic weights of its own and uses its own field norm: it is "
+            "a different function class, e2cnn checkpoints cannot be loaded, and there is no bridge for them.", ("irrep_",))
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     @staticmethod
     def _bank(conv: SteerableConv, cache: bool) -> torch.Tensor:
-        """conv's dense bank, channels-last; in eval without autograd cached (on the layer) per weight version."""
+        """conv's dense bank, channels-last; in eval without autograd kept on the layer."""
         if not cache:
             return conv.expanded_weights().contiguous(memory_format=torch.channels_last)
-        key = (conv.weights._version, str(conv.weights.device), conv.weights.dtype)
-        hit = conv._cached_bank
-        if hit is None or hit[0] != key:
-            hit = conv._cached_bank = (key, conv.expanded_weights().detach().contiguous(memory_format=torch.channels_last))
-        return hit[1]
+        return conv._cache.get("bank", (conv.weights, conv.kernel_parts, conv.blocks),
+                               lambda: conv.expanded_weights().detach().contiguous(memory_format=torch.channels_last))
 
     def _conv(self, h: torch.Tensor, conv: SteerableConv, infer: bool) -> torch.Tensor:
         """conv on the channels-last device map h: the FFT convolution where its own gate admits the dense bank, else the library's."""
@@ -374,10 +366,7 @@ class ESCNNSteerableNetwork(nn.Module):
             if not infer:
                 return fftconv.ConvKxKFunction.apply(h, conv.expanded_weights())
             bank = self._bank(conv, True)
-            hit = conv._cached_spectra
-            if hit is None or hit[0] is not bank:                 # the filter spectra live as long as the cached bank they come from
-                hit = conv._cached_spectra = (bank, fftconv.spectra_for_k(bank))
-            return fftconv.conv_kxk(h, hit[1], k, None, False)
+            return fftconv.conv_kxk(h, conv._cache.derived("bank", "fft", lambda: fftconv.spectra_for_k(bank)), k, None, False)
         return F.conv2d(h, self._bank(conv, infer))
 
     @staticmethod

@@ -36,6 +36,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from equiadapt_amd import ops
+from equiadapt_amd.common.derived import DerivedCache, bn_eval_affine, refuse_e2cnn_state_dict
 from equiadapt_amd.images.canonicalization_networks import fftconv, winograd
 from equiadapt_amd.images.canonicalization_networks.custom_group_equivariant_layers import (
     RotationEquivariantConv,
@@ -96,25 +97,10 @@ class _ExactQuarterTurns:
     equivariant to 4e-7 of its output only, in fp64 as well, where e2cnn's C4 / D4 networks are equivariant to rounding.  Here the
     matrices are rounded to the permutation they stand for.  Other rotation counts: the layer's own bank."""
 
-    def expanded_weights(self) -> torch.Tensor:
+    def _action_matrices(self, w: torch.Tensor) -> torch.Tensor:
         if 4 % self.num_rotations:
-            return super().expanded_weights()
-        w = self.weights
-        keep = not self.training and not torch.is_grad_enabled()
-        if keep:
-            ver, bank = self._cached_bank
-            if ver == w._version and bank is not None and bank.device == w.device and bank.dtype == w.dtype:
-                return bank
-        O, I, E, k = self.out_channels, self.in_channels, self.num_group_elements, self.kernel_size
-        A = filter_action_matrices(k, self.num_rotations, self.reflections, w.device).round().to(w.dtype)     # (E, p, q), entries 0 / 1
-        if self.lifting:
-            bank = torch.einsum("epq,oiq->oeip", A, w.reshape(O, I, k * k)).reshape(O * E, I, k, k)
-        else:
-            wp = w.reshape(O, I, E, k * k)[:, :, self.src_slot]            # (O, I, E[e], E[m], q)
-            bank = torch.einsum("epq,oiemq->oeimp", A, wp).reshape(O * E, I * E, k, k)
-        if keep:
-            self._cached_bank = (w._version, bank)
-        return bank
+            return super()._action_matrices(w)
+        return filter_action_matrices(self.kernel_size, self.num_rotations, self.reflections, w.device).round().to(w.dtype)   # entries 0 / 1
 
 
 class _Lift(_ExactQuarterTurns, RotationEquivariantConvLift):
@@ -261,63 +247,37 @@ class ESCNNWRNEquivariantNetwork(nn.Module):
         mods.append(conv(n4, n5, kernel_size, num_rotations, device="cpu"))
         self.eqv_network = nn.Sequential(*mods)
         self.last_routes: List[str] = []
-        self._fold_cache: dict = {}
+        self._cache = DerivedCache()
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         """A checkpoint of the reference's e2cnn network (escnn_networks.py:376-485) cannot be loaded by key: e2cnn stores a flat
         coefficient vector per layer over its steerable basis (``...weights`` 1-D, ``...basisexpansion...`` / ``...filter``
         buffers), this network stores rotated filter banks.  Say so instead of failing on a shape mismatch."""
-        own = prefix + "eqv_network."
-        for k, v in state_dict.items():
-            if k.startswith(own) and ("basisexpansion" in k or k.endswith(".filter") or k.endswith(".expanded_bias")
-                                      or (k.endswith(".weights") and getattr(v, "dim", lambda: 2)() == 1)):
-                raise RuntimeError(
-                    f"state_dict key {k!r} comes from e2cnn's steerable-basis parameterisation (the reference's "
-                    "ESCNNWRNEquivariantNetwork). equiadapt_amd.ESCNNWRNEquivariantNetwork parameterises its layers by rotated filter "
-                    "banks and cannot load it by key.")
+        refuse_e2cnn_state_dict(
+            state_dict, prefix + "eqv_network.", "ESCNNWRNEquivariantNetwork",
+            "equiadapt_amd.ESCNNWRNEquivariantNetwork parameterises its layers by rotated filter banks and cannot load it by key.",
+            (".expanded_bias",))
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    # -- fused route: folded operands, cached per parameter version -------------------------------------------------------
-    @staticmethod
-    def _key(*tensors) -> tuple:
-        return tuple((-1, 0) if v is None else (v._version, v.data_ptr()) for v in tensors)
-
+    # -- fused route: folded operands, kept in self._cache under the layer; what is built from a bank under (layer, tag) -------------
     def _fold(self, conv, bn) -> Tuple[torch.Tensor, torch.Tensor]:
         """Channels-last filter bank and per-channel bias of ``bn(conv(.))`` in eval mode (bn None: of conv)."""
-        key = self._key(conv.weights, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
-        hit = self._fold_cache.get(id(conv))
-        if hit is not None and hit[0] == key:
-            return hit[1], hit[2]
-        bank = conv.expanded_weights()
-        bias = conv.bias if conv.bias is not None else bank.new_zeros(conv.out_channels)
-        if bn is not None:
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)                  # per field
-            bias = (bias - bn.running_mean) * scale + bn.bias
-            bank = bank * scale.repeat_interleave(conv.num_group_elements)[:, None, None, None]
-        bank = bank.contiguous(memory_format=torch.channels_last)
-        bias = bias.repeat_interleave(conv.num_group_elements).contiguous()
-        self._fold_cache[id(conv)] = (key, bank, bias)
-        return bank, bias
+        def build():
+            bank = conv.expanded_weights()
+            bias = conv.bias if conv.bias is not None else bank.new_zeros(conv.out_channels)
+            if bn is not None:
+                scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)                  # per field
+                bias = (bias - bn.running_mean) * scale + bn.bias
+                bank = bank * scale.repeat_interleave(conv.num_group_elements)[:, None, None, None]
+            return bank.contiguous(memory_format=torch.channels_last), bias.repeat_interleave(conv.num_group_elements).contiguous()
 
-    def _derived(self, conv, build, *tag):
-        """Something built from conv's folded bank (packed weights, filter spectra), kept for as long as `_fold`'s entry keeps its key."""
-        key = self._fold_cache[id(conv)][0]
-        hit = self._fold_cache.get((*tag, id(conv)))
-        if hit is None or hit[0] != key:
-            hit = (key, build())
-            self._fold_cache[(*tag, id(conv))] = hit
-        return hit[1]
+        norm = () if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        return self._cache.get(conv, (conv.weights, conv.bias, *norm), build)
 
     def _affine(self, bn) -> Tuple[torch.Tensor, torch.Tensor]:
         """(s, t) per channel of an InnerBatchNorm in eval mode."""
-        key = self._key(bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        hit = self._fold_cache.get(id(bn))
-        if hit is None or hit[0] != key:
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            s, t = torch.stack([scale, bn.bias - bn.running_mean * scale]).repeat_interleave(self.num_group_elements, dim=1)
-            hit = (key, s, t)
-            self._fold_cache[id(bn)] = hit
-        return hit[1], hit[2]
+        return self._cache.get(bn, (bn.weight, bn.bias, bn.running_mean, bn.running_var),
+                               lambda: tuple(torch.stack(bn_eval_affine(bn)).repeat_interleave(self.num_group_elements, dim=1)))
 
     def _conv1x1(self, h, conv, bn, res, affine, relu: bool, routes: List[str]) -> torch.Tensor:
         """act(bn(conv(h)) [+ res]), act = [relu] o affine, for a 1 x 1 layer on the channels-last map h: one launch of
@@ -326,7 +286,7 @@ class ESCNNWRNEquivariantNetwork(nn.Module):
         cout, cin = bank.shape[:2]
         s, t = affine if affine is not None else (None, None)
         if ops.gconv1x1_supported(h.shape[0] * h.shape[2] * h.shape[3], cin, cout):
-            wpk = self._derived(conv, lambda: ops.pack_gconv1x1_weights(bank), "gconv1x1")
+            wpk = self._cache.derived(conv, (conv, "gconv1x1"), lambda: ops.pack_gconv1x1_weights(bank))
             routes.append("gconv1x1" if res is None else "gconv1x1+junction")
             return ops.gconv1x1_nhwc(h.contiguous(memory_format=torch.channels_last), wpk, bias,
                                      None if res is None else res.contiguous(memory_format=torch.channels_last), s, t, relu)
@@ -348,14 +308,14 @@ class ESCNNWRNEquivariantNetwork(nn.Module):
         hp = hp.contiguous(memory_format=torch.channels_last)
         if k == 5 and fftconv.applicable(hp, cin, cout):
             routes.append("fft5")
-            return fftconv.conv5x5(hp, self._derived(conv, lambda: fftconv.spectra_for_k(bank), "fft"), bias, relu)
+            return fftconv.conv5x5(hp, self._cache.derived(conv, (conv, "fft"), lambda: fftconv.spectra_for_k(bank)), bias, relu)
         if k != 5 and fftconv.applicable_k(hp.shape, cin, cout, k, hp.device):
             routes.append("fftk")
-            return fftconv.conv_kxk(hp, self._derived(conv, lambda: fftconv.spectra_for_k(bank), "fft"), k, bias, relu)
+            return fftconv.conv_kxk(hp, self._cache.derived(conv, (conv, "fft"), lambda: fftconv.spectra_for_k(bank)), k, bias, relu)
         if k == 5 and winograd.applicable(hp, cin, cout):
             m = winograd.tile_for(hp)
             routes.append("wino")
-            return winograd.conv5x5(hp, self._derived(conv, lambda: winograd.transform_filters(bank, m), "wino", m), bias, relu)
+            return winograd.conv5x5(hp, self._cache.derived(conv, (conv, "wino", m), lambda: winograd.transform_filters(bank, m)), bias, relu)
         routes.append("lib")
         y = F.conv2d(hp, bank, bias)
         return torch.relu_(y) if relu else y
@@ -375,7 +335,7 @@ class ESCNNWRNEquivariantNetwork(nn.Module):
         k = stem.kernel_size
         if stem.mfma_lifting_ok(h):
             narrow = ops.lift_conv_supported(bank.shape[1], k, k, bank.shape[0])
-            wpk = self._derived(stem, lambda: (ops.pack_lift_weights if narrow else ops.pack_lift_weights_wide)(bank), "lift")
+            wpk = self._cache.derived(stem, (stem, "lift"), lambda: (ops.pack_lift_weights if narrow else ops.pack_lift_weights_wide)(bank))
             routes.append("lift" if narrow else "lift_wide")
             h = (ops.lift_conv_nhwc if narrow else ops.lift_conv_wide)(h, wpk, bias, True, k, k)
         else:

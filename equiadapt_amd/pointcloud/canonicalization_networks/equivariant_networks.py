@@ -10,6 +10,7 @@ from typing import Any, Optional
 import torch
 import torch.nn as nn
 
+from equiadapt_amd.common.derived import DerivedCache, bn_eval_affine
 from equiadapt_amd.common.utils import mark_written, update_running_stats
 
 from equiadapt_amd.pointcloud.canonicalization_networks.vector_neuron_layers import (
@@ -282,6 +283,7 @@ class VNSmall(nn.Module):
         self.bn1 = VNBatchNorm(64 // 3, dim=4)
         self.conv2 = VNLinearLeakyReLU(64 // 3, 12 // 3, dim=4, negative_slope=0.0)
         self.dropout = nn.Dropout(p=0.5)
+        self._cache = DerivedCache()
         if self.pooling == "max":
             self.pool = VNMaxPool(64 // 3)
         elif self.pooling == "mean":
@@ -291,33 +293,22 @@ class VNSmall(nn.Module):
 
     def packed_parameters(self) -> torch.Tensor:
         """The 1310 floats the fused kernel consumes (layout: vn_prm in csrc/vn_common.hpp), eval-mode batch-norms folded to a
-        scale/shift of the vector norm; "max" pooling: + the 441 of the pooling layer's direction map.  Cached per parameter
-        version."""
-        tensors = list(self.parameters()) + [b for b in self.buffers()]
-        key = tuple(t._version for t in tensors) + (str(tensors[0].device),)
-        hit = getattr(self, "_packed", None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
+        scale/shift of the vector norm; "max" pooling: + the 441 of the pooling layer's direction map."""
+        def build():
+            parts = []
+            for lay, bn in ((self.conv_pos, self.conv_pos.batchnorm.bn2d), (self.conv1, self.conv1.batchnorm.bn1d)):
+                parts += [lay.map_to_feat.weight.flatten(), lay.map_to_dir.weight.flatten(), *bn_eval_affine(bn)]
+            parts += bn_eval_affine(self.bn1.bn1d)
+            parts += [self.conv2.map_to_feat.weight.flatten(), self.conv2.map_to_dir.weight.flatten(), *bn_eval_affine(self.conv2.batchnorm.bn1d)]
+            if self.pooling == "max":
+                parts.append(self.pool.map_to_dir.weight.flatten())
+            packed = torch.cat([p.detach().float() for p in parts]).contiguous()
+            from equiadapt_amd import ops
 
-        def fold(bn):
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            return scale, bn.bias - bn.running_mean * scale
+            assert packed.numel() == (ops.VNSMALL_PARAMS_MAX if self.pooling == "max" else ops.VNSMALL_PARAMS)
+            return packed
 
-        parts = []
-        for lay, bn in ((self.conv_pos, self.conv_pos.batchnorm.bn2d), (self.conv1, self.conv1.batchnorm.bn1d)):
-            sc, sh = fold(bn)
-            parts += [lay.map_to_feat.weight.flatten(), lay.map_to_dir.weight.flatten(), sc, sh]
-        parts += list(fold(self.bn1.bn1d))
-        sc, sh = fold(self.conv2.batchnorm.bn1d)
-        parts += [self.conv2.map_to_feat.weight.flatten(), self.conv2.map_to_dir.weight.flatten(), sc, sh]
-        if self.pooling == "max":
-            parts.append(self.pool.map_to_dir.weight.flatten())
-        packed = torch.cat([p.detach().float() for p in parts]).contiguous()
-        from equiadapt_amd import ops
-
-        assert packed.numel() == (ops.VNSMALL_PARAMS_MAX if self.pooling == "max" else ops.VNSMALL_PARAMS)
-        self._packed = (key, packed)
-        return packed
+        return self._cache.get("packed", [*self.parameters(), *self.buffers()], build)
 
     def fused_inference_applies(self, point_cloud: torch.Tensor) -> bool:
         """eval mode without autograd on the device, at a size the fused kernel takes (eqa_vnsmall_fwd / _canonicalize)."""

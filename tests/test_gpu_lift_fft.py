@@ -154,7 +154,7 @@ def test_network_inference_takes_the_fused_route(dev, monkeypatch):
     assert (fused - unfused).abs().max().item() <= 2e-6 * unfused.abs().max().item()
     assert torch.equal(fused.argmax(1), unfused.argmax(1))
     # the default form of the fused kernel is the fp16 one, its operand cached per weight version; the fp32 form gives the same activations
-    assert fftconv.LIFT_FFT_FORM == "h2" and ("lifth", id(net.eqv_network[0])) in net._fold_cache
+    assert fftconv.LIFT_FFT_FORM == "h2" and (net.eqv_network[0], "lifth") in net._cache
     monkeypatch.setenv("EQA_LIFT_FFT_FUSED", "1")
     monkeypatch.setattr(fftconv, "LIFT_FFT_FORM", "f32")
     with torch.no_grad():
@@ -166,7 +166,7 @@ def test_network_inference_takes_the_fused_route(dev, monkeypatch):
     with torch.no_grad():
         pieces_form = net(x)
         again = net(x)
-    assert ("liftp", id(net.eqv_network[0])) in net._fold_cache and torch.equal(pieces_form, again)
+    assert (net.eqv_network[0], "liftp") in net._cache and torch.equal(pieces_form, again)
     assert (pieces_form - unfused).abs().max().item() <= 2e-6 * unfused.abs().max().item()
     assert torch.equal(pieces_form.argmax(1), unfused.argmax(1))
 

@@ -45,6 +45,7 @@ PHI_SIGN = -1.0
 
 _FREQS = {"scalar": (0,), "fourier": tuple(range(MAX_FREQ + 1)), "vector": (1,)}
 _FOURIER_ACT_KERNEL = "EQA_FOURIER_KERNEL"     # "0": the op-by-op activation on the device as well (A/B timing, tools/kbench_fourier_act.py)
+_FIELD_NORM_KERNEL = "EQA_FIELD_NORM_KERNEL"   # "0": training keeps the norm in torch ops in front of FourierELUFunction (tools/kbench_field_norm.py)
 
 
 def sampling_matrix() -> torch.Tensor:
@@ -222,6 +223,73 @@ class SteerableConv(_Fp64Tables):
         return out.flatten(1, 2)
 
 
+def field_norm_scale_shift(sums: torch.Tensor, n: int, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                           dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`FieldNorm`'s batch statistics and affine map from the six sums per field over the n pixels of a map.
+    sums:(fields, 6) fp64 = sum a_0, sum a_0^2, sum (Re^2 + Im^2) of c_1..c_4.  Returns mean:(fields,) and var:(fields, 5) in fp64
+    (var_0 = max(E[a_0^2] - mean^2, 0), var_m = E[(Re^2 + Im^2) / 2]) and scale:(fields, 5), shift:(fields,) in `dtype`.  All of it
+    is fp64 arithmetic on the sums' device, each result rounded to `dtype` once; the shift is formed from the ROUNDED scale,
+    so that scale_0 a_0 + shift = scale_0 (a_0 - mean) + bias keeps its accuracy where the mean is large against the spread."""
+    sums = sums.double()
+    mean = sums[:, 0] / n
+    var0 = (sums[:, 1] / n - mean * mean).clamp_min(0.0)
+    var = torch.cat([var0[:, None], sums[:, 2:] / (2.0 * n)], dim=1)
+    scale = (weight.double() * torch.rsqrt(var + eps)).to(dtype)
+    shift = (bias.double() - mean * scale[:, 0].double()).to(dtype)
+    return mean, var, scale, shift
+
+
+def field_norm_backward_coefficients(bsums: torch.Tensor, weight: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, n: int,
+                                     eps: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The backward of `FieldNorm` (training mode) through its batch statistics, from six sums per field.
+    bsums:(fields, 6) fp64 = S_0 = sum du_0, S_1 = sum du_0 a_0, T_m = sum (du_Re Re + du_Im Im) of c_m, du the gradient at the norm's
+    output; mean, var: the batch statistics of `field_norm_scale_shift`.  With r = rsqrt(var + eps), scale = weight r and
+    D = r_0 (S_1 - mean S_0):  dbias = S_0,  dweight = (D, r_m T_m),  and the gradient at the norm's input is
+      dx_0 = scale_0 du_0 - k_0 - c_1 (a_0 - mean),  dx_j = scale_m du_j - c_{1+m} x_j  (both parts of frequency m),
+      k_0 = scale_0 S_0 / n,  c_1 = scale_0 r_0 D / n,  c_{1+m} = scale_m r_m^2 T_m / (2 n)
+    (the clamp of var_0 at zero passes its gradient, as `clamp_min` does at and above 0).
+    Returns coef:(fields, 7) = (k_0, mean, c_1..c_5), dweight:(fields, 5), dbias:(fields,), all fp64."""
+    bsums, mean, var = bsums.double(), mean.double(), var.double()
+    r = torch.rsqrt(var + eps)
+    scale = weight.double() * r
+    S0, S1, T = bsums[:, 0], bsums[:, 1], bsums[:, 2:]
+    D = r[:, 0] * (S1 - mean * S0)
+    dweight = torch.cat([D[:, None], r[:, 1:] * T], dim=1)
+    k0 = scale[:, 0] * S0 / n
+    c1 = scale[:, 0] * r[:, 0] * D / n
+    cm = scale[:, 1:] * r[:, 1:] ** 2 * T / (2.0 * n)
+    return torch.cat([k0[:, None], mean[:, None], c1[:, None], cm], dim=1), dweight, S0
+
+
+class FieldNormFourierELUFunction(torch.autograd.Function):
+    """FourierELU(FieldNorm(x)) with batch statistics on a channels-last fp32 device map: statistics (csrc/field_norm.hip), their
+    finalisation in fp64 torch ops on the device (no host synchronisation), `ops.fourier_elu` with the resulting scale / shift.
+    Returns (y, mean:(fields,), var:(fields, 5)), the statistics not differentiable (the running averages want them).  Saves x and
+    per-field tables only -- never the normed map: the backward is one reduction over (x, dy), the same finalisation, and one pass
+    that forms the activation's gradient again and writes dx."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        x = x.contiguous(memory_format=torch.channels_last)
+        n = x.shape[0] * x.shape[2] * x.shape[3]
+        mean, var, scale, shift = field_norm_scale_shift(ops.field_norm_stats(x).sum(0), n, weight.detach(), bias.detach(), eps)
+        ctx.save_for_backward(x, weight, scale, shift, mean, var)
+        ctx.eps, ctx.n = eps, n
+        mean32, var32 = mean.float(), var.float()
+        ctx.mark_non_differentiable(mean32, var32)
+        return ops.fourier_elu(x, scale, shift), mean32, var32
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _dmean, _dvar):
+        x, weight, scale, shift, mean, var = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        bsums = ops.field_norm_elu_bwd_reduce(x, dy, scale, shift).sum(0)
+        coef, dweight, dbias = field_norm_backward_coefficients(bsums, weight, mean, var, ctx.n, ctx.eps)
+        dx = ops.field_norm_elu_bwd_apply(x, dy, scale, shift, coef.float()) if ctx.needs_input_grad[0] else None
+        return dx, dweight.to(weight.dtype), dbias.to(weight.dtype), None
+
+
 class FieldNorm(nn.Module):
     """This package's norm for "fourier" fields, in the place of e2cnn's ``GNormBatchNorm`` (whose arithmetic cannot be checked
     here): frequency 0 is ordinary batch norm over (B, H, W) with weight and bias; frequency m >= 1 is
@@ -276,6 +344,25 @@ class FieldNorm(nn.Module):
         shift9 = F.pad(shift[:, None], (0, FIELD_DIM - 1)).reshape(1, C * FIELD_DIM, 1, 1)
         return x * scale9 + shift9
 
+    def forward_elu(self, x: torch.Tensor) -> torch.Tensor:
+        """FourierELU(self(x)) in training mode on a channels-last fp32 device map, on the kernels (`FieldNormFourierELUFunction`),
+        with the running-statistics update of `forward`."""
+        y, mean, var = FieldNormFourierELUFunction.apply(x, self.weight, self.bias, self.eps)
+        n = x.shape[0] * x.shape[2] * x.shape[3]
+        with torch.no_grad():
+            unbiased = torch.cat([var[:, :1] * (n / max(n - 1, 1)), var[:, 1:]], dim=1)
+            self.running_mean.mul_(1.0 - self.momentum).add_(mean.to(self.running_mean.dtype), alpha=self.momentum)
+            self.running_var.mul_(1.0 - self.momentum).add_(unbiased.to(self.running_var.dtype), alpha=self.momentum)
+            self.num_batches_tracked += 1
+        return y
+
+
+def fused_field_norm(norm: FieldNorm) -> bool:
+    """Whether a hidden block of the device path runs `norm.forward_elu`: the norm takes batch statistics, neither kernel knob is
+    off, and the field-norm kernels take its field count."""
+    return (norm.training and os.environ.get(_FOURIER_ACT_KERNEL, "1") != "0" and os.environ.get(_FIELD_NORM_KERNEL, "1") != "0"
+            and norm.fields <= ops.FIELD_NORM_MAX_FIELDS)
+
 
 class FourierELUFunction(torch.autograd.Function):
     """y = A^+ ELU(A x) on a channels-last fp32 device map, forward and backward on the kernels of csrc/fourier_act.hip.  Saves x
@@ -319,7 +406,9 @@ class ESCNNSteerableNetwork(nn.Module):
     CPU tensors and fp64 run through plain torch ops (``self.block``, then the spatial mean).  fp32 device tensors run the same
     layers channels-last with the activation on the HIP kernels: in eval mode without autograd the norm's running statistics fold
     into the kernel's scale / shift (norm + activation: one pass over the map) and the dense banks are cached per weight version;
-    otherwise the norm stays in torch ops and the activation is `FourierELUFunction`.  A hidden -> hidden convolution whose shape
+    a norm in training mode is `FieldNorm.forward_elu` (batch statistics, norm + activation and their backward on the kernels of
+    csrc/field_norm.hip and csrc/fourier_act.hip); otherwise (a frozen norm inside a training step, more fields than those kernels
+    take, `EQA_FIELD_NORM_KERNEL=0`) the norm stays in torch ops and the activation is `FourierELUFunction`.  A hidden -> hidden convolution whose shape
     `fftconv.applicable_k` admits is the overlap-save FFT convolution (`fftconv.conv_kxk` / `fftconv.ConvKxKFunction`), every other
     one the library's on channels-last.  The tail (last convolution + spatial mean) is linear, so where the window-sum kernels take
     the shape it is window sums times the tail bank."""
@@ -391,6 +480,8 @@ class ESCNNSteerableNetwork(nn.Module):
             h = self._conv(h, conv, infer)
             if not kernel:
                 h = act(norm(h)).contiguous(memory_format=torch.channels_last)
+            elif fused_field_norm(norm):
+                h = norm.forward_elu(h)
             elif infer and not norm.training:
                 h = ops.fourier_elu(h.contiguous(memory_format=torch.channels_last), *norm.folded())
             else:

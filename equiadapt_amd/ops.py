@@ -1226,7 +1226,71 @@ def fourier_elu_bwd(x: torch.Tensor, dy: torch.Tensor, scale: Optional[torch.Ten
     return dx
 
 
-VNDEEPSETS_WIDTHS = (8, 16, 32)   # hidden widths the kernels are compiled for (csrc/nbody.hip); the caller zero-pads others
+FIELD_NORM_MAX_FIELDS = 64   # == eqa_field_norm_max_fields() (csrc/field_norm.hip: one field per thread for a block's whole walk)
+
+
+def _field_norm_args(x: torch.Tensor, dy: Optional[torch.Tensor], scale, shift, what: str):
+    """`_fourier_args`, the field limit of the training kernels, dy shaped and laid out like x, and the rows of `partial`."""
+    npix, fields, keep, p_scale, p_shift = _fourier_args(x, scale, shift, what)
+    if fields > FIELD_NORM_MAX_FIELDS:
+        raise _lib.EqaLibraryError(f"{what}: {fields} fields, the field-norm kernels take at most {FIELD_NORM_MAX_FIELDS}")
+    if dy is not None and not (isinstance(dy, torch.Tensor) and dy.is_cuda and dy.dtype == torch.float32 and dy.shape == x.shape
+                               and dy.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError(f"{what} expects dy channels-last fp32 on the device, shaped like x")
+    blocks = int(_lib.load().eqa_field_norm_blocks(npix, fields)) if npix else 0
+    if npix and blocks <= 0:
+        _lib.check(blocks, "eqa_field_norm_blocks")
+    return npix, fields, keep, p_scale, p_shift, blocks
+
+
+def field_norm_stats(x: torch.Tensor) -> torch.Tensor:
+    """partial:(blocks, fields, 6) fp64 of a channels-last (B, 9 * fields, H, W) map (eqa_field_norm_stats): per block of the walk
+    and field sum a_0, sum a_0^2, sum (Re^2 + Im^2) of c_1..c_4.  ``partial.sum(0)`` are the sums over the map."""
+    lib = _lib.load()
+    npix, fields, _, _, _, blocks = _field_norm_args(x, None, None, None, "field_norm_stats")
+    partial = torch.empty((blocks, fields, 6), dtype=torch.float64, device=x.device)
+    if npix == 0:
+        return partial
+    with torch.cuda.device(x.device), _timed("field_norm_stats"):
+        st = lib.eqa_field_norm_stats(x.data_ptr(), partial.data_ptr(), npix, fields, _stream())
+    _lib.check(st, "eqa_field_norm_stats")
+    return partial
+
+
+def field_norm_elu_bwd_reduce(x: torch.Tensor, dy: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """partial:(blocks, fields, 6) fp64 (eqa_field_norm_elu_bwd_reduce): with du the gradient of `fourier_elu(x, scale, shift)` at
+    u = scale x + shift, per block and field sum du_0, sum du_0 a_0, sum (du_Re Re + du_Im Im) of c_1..c_4."""
+    lib = _lib.load()
+    npix, fields, keep, p_scale, p_shift, blocks = _field_norm_args(x, dy, scale, shift, "field_norm_elu_bwd_reduce")
+    partial = torch.empty((blocks, fields, 6), dtype=torch.float64, device=x.device)
+    if npix == 0:
+        return partial
+    with torch.cuda.device(x.device), _timed("field_norm_elu_bwd_reduce"):
+        st = lib.eqa_field_norm_elu_bwd_reduce(x.data_ptr(), p_scale, p_shift, dy.data_ptr(), partial.data_ptr(), npix, fields, _stream())
+    _lib.check(st, "eqa_field_norm_elu_bwd_reduce")
+    return partial
+
+
+def field_norm_elu_bwd_apply(x: torch.Tensor, dy: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                             coef: torch.Tensor) -> torch.Tensor:
+    """dx of the training-mode field norm + FourierELU (eqa_field_norm_elu_bwd_apply).  coef:(fields, 7) = (k_0, mean, c_1..c_5):
+    dx_0 = scale_0 du_0 - k_0 - c_1 (a_0 - mean), dx_j = scale_m du_j - c_{1+m} x_j; du is formed again from x and dy."""
+    lib = _lib.load()
+    npix, fields, keep, p_scale, p_shift, _ = _field_norm_args(x, dy, scale, shift, "field_norm_elu_bwd_apply")
+    coef = _need(coef, "coef")
+    if tuple(coef.shape) != (fields, 7):
+        raise ValueError(f"field_norm_elu_bwd_apply: coef must be (fields, 7) = ({fields}, 7), got {tuple(coef.shape)}")
+    dx = torch.empty_like(x)
+    if npix == 0:
+        return dx
+    with torch.cuda.device(x.device), _timed("field_norm_elu_bwd_apply"):
+        st = lib.eqa_field_norm_elu_bwd_apply(x.data_ptr(), p_scale, p_shift, dy.data_ptr(), coef.data_ptr(), dx.data_ptr(), npix,
+                                              fields, _stream())
+    _lib.check(st, "eqa_field_norm_elu_bwd_apply")
+    return dx
+
+
+VNDEEPSETS_WIDTHS = (8, 16, 32)  # hidden widths the kernels are compiled for (csrc/nbody.hip); the caller zero-pads others
 VNDEEPSETS_MAX_HIDDEN = 32
 VNDEEPSETS_MAX_LAYERS = 8         # == kMaxLayers
 NBODY_EDGES_OK = 4            # eqa_nbody_adjacency's flag when every edge stays inside a system and node M-1 has an incoming one

@@ -830,6 +830,36 @@ int eqa_fourier_elu_bwd(const float* x, const float* scale, const float* shift, 
                         void* stream);
 
 /*
+ * The field norm in front of FourierELU in training mode (ESCNNSteerableNetwork: batch statistics, and the backward through them;
+ * reference network: escnn_networks.py:187, GNormBatchNorm, here this package's field norm).  Maps x, dy, dx as in the FourierELU
+ * block above: channels-last (npix, 9 * fields) fp32, 16-byte aligned.  Per field the norm is u = scale (.) x + shift with
+ * scale = weight (.) rsqrt(var + eps), shift = bias - mean scale_0, var_0 = E[a_0^2] - mean^2, var_m = E[(Re^2 + Im^2) / 2] of c_m.
+ *   eqa_field_norm_max_fields      the largest `fields` the three kernels take (each thread keeps one field for its whole walk)
+ *   eqa_field_norm_blocks          rows of the `partial` buffers for (npix, fields); <= 0 (the error code) for sizes the kernels refuse
+ *   eqa_field_norm_stats           partial:(blocks, fields, 6) fp64, per block and field: sum a_0, sum a_0^2, sum (Re^2 + Im^2) of
+ *                                  c_m for m = 1..4.  The forward is these sums, added over the blocks and turned into scale /
+ *                                  shift by the caller, then eqa_fourier_elu_fwd.
+ *   eqa_field_norm_elu_bwd_reduce  with du = A^T [ELU'(A u) (.) (A dy / 16)] (eqa_fourier_elu_bwd before its multiply by scale):
+ *                                  partial:(blocks, fields, 6) fp64 = S_0 = sum du_0, S_1 = sum du_0 a_0, T_m = sum (du_Re Re +
+ *                                  du_Im Im) of frequency m for m = 1..4
+ *   eqa_field_norm_elu_bwd_apply   coef:(fields, 7) fp32 = (k_0, mean, c_1, .., c_5):  dx_0 = scale_0 du_0 - k_0 - c_1 (a_0 - mean),
+ *                                  dx_j = scale_m du_j - c_{1+m} x_j for the two parts of frequency m; du is formed again from x
+ *                                  and dy (no map but x and dy is read)
+ * scale:(fields, 5), shift:(fields) as in the FourierELU block (NULL: ones / zeros).  Every sum is fp64 from the first add (fp32
+ * terms and factors are converted first, so products are exact) in a fixed order, without atomics: two launches on the same input
+ * give the same bits.  fields > eqa_field_norm_max_fields(): EQA_ERR_UNSUPPORTED before any pointer is looked at; NULL x / dy / dx /
+ * partial / coef, npix <= 0 or fields <= 0: EQA_ERR_INVALID_ARG; misaligned maps: EQA_ERR_UNSUPPORTED.  Added without touching an
+ * existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_field_norm_max_fields(void);
+long long eqa_field_norm_blocks(long long npix, int fields);
+int eqa_field_norm_stats(const float* x, double* partial, long long npix, int fields, void* stream);
+int eqa_field_norm_elu_bwd_reduce(const float* x, const float* scale, const float* shift, const float* dy, double* partial,
+                                  long long npix, int fields, void* stream);
+int eqa_field_norm_elu_bwd_apply(const float* x, const float* scale, const float* shift, const float* dy, const float* coef, float* dx,
+                                 long long npix, int fields, void* stream);
+
+/*
  * VNDeepSets, the n-body canonicalization network (equiadapt/nbody/canonicalization_networks/custom_equivariant_networks.py:13-281),
  * for systems of 5 bodies: S systems, M = 5 S nodes.  loc, vel:(M,3); charges:(M,1) or (M); vel / charges NULL when the feature
  * string does not use them.  features: bit 0 = velocity, bit 1 = angular momentum, bit 2 = charge ("p" 0, "pv" 1, "pva" 3,

@@ -46,6 +46,7 @@ PHI_SIGN = -1.0
 _FREQS = {"scalar": (0,), "fourier": tuple(range(MAX_FREQ + 1)), "vector": (1,)}
 _FOURIER_ACT_KERNEL = "EQA_FOURIER_KERNEL"     # "0": the op-by-op activation on the device as well (A/B timing, tools/kbench_fourier_act.py)
 _FIELD_NORM_KERNEL = "EQA_FIELD_NORM_KERNEL"   # "0": training keeps the norm in torch ops in front of FourierELUFunction (tools/kbench_field_norm.py)
+_STEER_LIFT_KERNEL = "EQA_STEER_LIFT_KERNEL"   # "0": the first layer stays the library's convolution (A/B timing, tools/kbench_steer_lift.py)
 
 
 def sampling_matrix() -> torch.Tensor:
@@ -266,13 +267,17 @@ class FieldNormFourierELUFunction(torch.autograd.Function):
     finalisation in fp64 torch ops on the device (no host synchronisation), `ops.fourier_elu` with the resulting scale / shift.
     Returns (y, mean:(fields,), var:(fields, 5)), the statistics not differentiable (the running averages want them).  Saves x and
     per-field tables only -- never the normed map: the backward is one reduction over (x, dy), the same finalisation, and one pass
-    that forms the activation's gradient again and writes dx."""
+    that forms the activation's gradient again and writes dx.
+    sums: the (fields, 6) fp64 sums of x where the kernel that wrote x took them on the way out (`SteerLiftFunction`); then
+    `ops.field_norm_stats` is not launched."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps):
+    def forward(ctx, x, weight, bias, eps, sums=None):
         x = x.contiguous(memory_format=torch.channels_last)
         n = x.shape[0] * x.shape[2] * x.shape[3]
-        mean, var, scale, shift = field_norm_scale_shift(ops.field_norm_stats(x).sum(0), n, weight.detach(), bias.detach(), eps)
+        if sums is None:
+            sums = ops.field_norm_stats(x).sum(0)
+        mean, var, scale, shift = field_norm_scale_shift(sums, n, weight.detach(), bias.detach(), eps)
         ctx.save_for_backward(x, weight, scale, shift, mean, var)
         ctx.eps, ctx.n = eps, n
         mean32, var32 = mean.float(), var.float()
@@ -287,7 +292,7 @@ class FieldNormFourierELUFunction(torch.autograd.Function):
         bsums = ops.field_norm_elu_bwd_reduce(x, dy, scale, shift).sum(0)
         coef, dweight, dbias = field_norm_backward_coefficients(bsums, weight, mean, var, ctx.n, ctx.eps)
         dx = ops.field_norm_elu_bwd_apply(x, dy, scale, shift, coef.float()) if ctx.needs_input_grad[0] else None
-        return dx, dweight.to(weight.dtype), dbias.to(weight.dtype), None
+        return dx, dweight.to(weight.dtype), dbias.to(weight.dtype), None, None
 
 
 class FieldNorm(nn.Module):
@@ -344,10 +349,10 @@ class FieldNorm(nn.Module):
         shift9 = F.pad(shift[:, None], (0, FIELD_DIM - 1)).reshape(1, C * FIELD_DIM, 1, 1)
         return x * scale9 + shift9
 
-    def forward_elu(self, x: torch.Tensor) -> torch.Tensor:
+    def forward_elu(self, x: torch.Tensor, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
         """FourierELU(self(x)) in training mode on a channels-last fp32 device map, on the kernels (`FieldNormFourierELUFunction`),
-        with the running-statistics update of `forward`."""
-        y, mean, var = FieldNormFourierELUFunction.apply(x, self.weight, self.bias, self.eps)
+        with the running-statistics update of `forward`.  sums: x's (fields, 6) sums, where its producer took them."""
+        y, mean, var = FieldNormFourierELUFunction.apply(x, self.weight, self.bias, self.eps, sums)
         n = x.shape[0] * x.shape[2] * x.shape[3]
         with torch.no_grad():
             unbiased = torch.cat([var[:, :1] * (n / max(n - 1, 1)), var[:, 1:]], dim=1)
@@ -362,6 +367,41 @@ def fused_field_norm(norm: FieldNorm) -> bool:
     off, and the field-norm kernels take its field count."""
     return (norm.training and os.environ.get(_FOURIER_ACT_KERNEL, "1") != "0" and os.environ.get(_FIELD_NORM_KERNEL, "1") != "0"
             and norm.fields <= ops.FIELD_NORM_MAX_FIELDS)
+
+
+class SteerLiftFunction(torch.autograd.Function):
+    """The scalar -> Fourier-field convolution of the first layer on the kernels of csrc/steer_lift.hip: y = conv2d(x, bank) on a
+    channels-last fp32 device map (`ops.steer_lift`), filter gradient on the matrix cores too (`ops.steer_lift_wgrad`).  The input
+    image needs no gradient in the canonicalizer; if asked for, it is the framework's.  with_stats: also return the (fields, 6)
+    fp64 sums the field norm behind the layer needs, taken in the kernel's epilogue (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, x, bank, with_stats=False):
+        ctx.save_for_backward(x, bank)
+        k, fields = bank.shape[-1], bank.shape[0] // FIELD_DIM
+        y, sums = ops.steer_lift(x, ops.pack_steer_lift_weights(bank.detach()), k, fields, with_stats)
+        if with_stats:
+            ctx.mark_non_differentiable(sums)
+            return y, sums
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, *_):
+        x, bank = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = torch.nn.grad.conv2d_input(x.shape, bank, dy) if ctx.needs_input_grad[0] else None
+        dbank = ops.steer_lift_wgrad(x, dy, bank.shape[-1]) if ctx.needs_input_grad[1] else None
+        return dx, dbank, None
+
+
+def steer_lift_route(conv: "SteerableConv", h: torch.Tensor) -> bool:
+    """Whether `conv` on the channels-last fp32 device map h runs on the steerable lifting kernels: a scalar -> Fourier-field layer of a
+    shape they take, a map of at least k x k, and the knob not off.
+    Measured exclusions (tools/kbench_steer_lift.py, profiles/steer_lift/): see DESIGN.md, ESCNNSteerableNetwork / Speed."""
+    k = conv.kernel_size
+    return (conv.in_kind == "scalar" and conv.out_kind == "fourier" and os.environ.get(_STEER_LIFT_KERNEL, "1") != "0"
+            and h.shape[0] > 0 and h.shape[2] >= k and h.shape[3] >= k and ops.steer_lift_supported(conv.in_fields, k, conv.out_fields))
 
 
 class FourierELUFunction(torch.autograd.Function):
@@ -410,7 +450,10 @@ class ESCNNSteerableNetwork(nn.Module):
     csrc/field_norm.hip and csrc/fourier_act.hip); otherwise (a frozen norm inside a training step, more fields than those kernels
     take, `EQA_FIELD_NORM_KERNEL=0`) the norm stays in torch ops and the activation is `FourierELUFunction`.  A hidden -> hidden convolution whose shape
     `fftconv.applicable_k` admits is the overlap-save FFT convolution (`fftconv.conv_kxk` / `fftconv.ConvKxKFunction`), every other
-    one the library's on channels-last.  The tail (last convolution + spatial mean) is linear, so where the window-sum kernels take
+    one the library's on channels-last.  The first layer (scalar -> Fourier fields) is the fused lifting kernel of
+    csrc/steer_lift.hip where `steer_lift_route` admits it (`SteerLiftFunction` in training, which also hands the norm behind it
+    its batch sums); `EQA_STEER_LIFT_KERNEL=0` keeps the library's convolution.  ``last_routes``: one word per convolution of the
+    last device forward ("steer_lift", "fft", "lib", "window_sums").  The tail (last convolution + spatial mean) is linear, so where the window-sum kernels take
     the shape it is window sums times the tail bank."""
 
     def __init__(self, in_shape: tuple, out_channels: int, kernel_size: int = 9, group_type: str = "rotation", num_layers: int = 1):
@@ -425,6 +468,7 @@ class ESCNNSteerableNetwork(nn.Module):
             fields, kind = out_channels, "fourier"
         mods.append(SteerableConv(fields, kind, 2, "vector", kernel_size))
         self.block = nn.Sequential(*mods)
+        self.last_routes: List[str] = []
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         """A checkpoint of the reference's e2cnn network cannot be loaded by key: e2cnn stores one flat coefficient vector per
@@ -446,47 +490,61 @@ class ESCNNSteerableNetwork(nn.Module):
         return conv._cache.get("bank", (conv.weights, conv.kernel_parts, conv.blocks),
                                lambda: conv.expanded_weights().detach().contiguous(memory_format=torch.channels_last))
 
-    def _conv(self, h: torch.Tensor, conv: SteerableConv, infer: bool) -> torch.Tensor:
-        """conv on the channels-last device map h: the FFT convolution where its own gate admits the dense bank, else the library's."""
+    def _conv(self, h: torch.Tensor, conv: SteerableConv, infer: bool, want_sums: bool = False):
+        """conv on the channels-last device map h -> (map, sums, route): the fused lifting kernel for the first layer, the FFT
+        convolution where its own gate admits the dense bank, else the library's.  sums: the (fields, 6) sums for the field norm
+        behind the layer where want_sums and the route takes them on the way out, else None."""
         k = conv.kernel_size
         cout, cin = conv.out_fields * conv.out_dim, conv.in_fields * conv.in_dim
+        if steer_lift_route(conv, h):
+            if not infer:
+                out = SteerLiftFunction.apply(h, conv.expanded_weights(), want_sums)
+                return (*out, "steer_lift") if want_sums else (out, None, "steer_lift")
+            bank = self._bank(conv, True)
+            wpk = conv._cache.derived("bank", "steer_lift", lambda: ops.pack_steer_lift_weights(bank))
+            return ops.steer_lift(h, wpk, k, conv.out_fields)[0], None, "steer_lift"
         if conv.in_kind == "fourier" and fftconv.applicable_k(h.shape, cin, cout, k, h.device,
                                                               h.is_contiguous(memory_format=torch.channels_last)):
             if not infer:
-                return fftconv.ConvKxKFunction.apply(h, conv.expanded_weights())
+                return fftconv.ConvKxKFunction.apply(h, conv.expanded_weights()), None, "fft"
             bank = self._bank(conv, True)
-            return fftconv.conv_kxk(h, conv._cache.derived("bank", "fft", lambda: fftconv.spectra_for_k(bank)), k, None, False)
-        return F.conv2d(h, self._bank(conv, infer))
+            return fftconv.conv_kxk(h, conv._cache.derived("bank", "fft", lambda: fftconv.spectra_for_k(bank)), k, None, False), None, "fft"
+        return F.conv2d(h, self._bank(conv, infer)), None, "lib"
 
     @staticmethod
-    def _tail(h: torch.Tensor, conv: SteerableConv, bank: torch.Tensor, infer: bool) -> torch.Tensor:
-        """Spatial mean of the last convolution, (B, 4).  Where the channels-last window-sum kernel takes the map: its k x k window
+    def _tail(h: torch.Tensor, conv: SteerableConv, bank: torch.Tensor, infer: bool) -> Tuple[torch.Tensor, str]:
+        """(spatial mean of the last convolution, (B, 4); its route).  Where the channels-last window-sum kernel takes the map: its k x k window
         sums (fp64) times the bank; else the convolution and a mean."""
         k = conv.kernel_size
         B, C, H, W = h.shape
         if (C % 4 == 0 and k <= ops.MAX_WINDOW_K and H > 2 * (k - 1) and W > 2 * (k - 1) and 0 < B <= 65535
                 and not h.is_contiguous() and h.is_contiguous(memory_format=torch.channels_last)):
             S = ops.window_sums(h, k) if infer else WindowSumsFunction.apply(h, k)           # (B, C, k, k) fp64
-            return (S.flatten(1) @ bank.double().flatten(1).t() / float((H - k + 1) * (W - k + 1))).float()
-        return F.conv2d(h, bank).mean(dim=(-2, -1))
+            return (S.flatten(1) @ bank.double().flatten(1).t() / float((H - k + 1) * (W - k + 1))).float(), "window_sums"
+        return F.conv2d(h, bank).mean(dim=(-2, -1)), "lib"
 
     def _forward_device(self, x: torch.Tensor) -> torch.Tensor:
         infer = not self.training and not torch.is_grad_enabled()
         kernel = os.environ.get(_FOURIER_ACT_KERNEL, "1") != "0"
         mods = list(self.block)
         h = x.contiguous(memory_format=torch.channels_last)
+        routes: List[str] = []
         for i in range(0, len(mods) - 1, 3):
             conv, norm, act = mods[i:i + 3]
-            h = self._conv(h, conv, infer)
+            fused = kernel and fused_field_norm(norm)
+            h, sums, route = self._conv(h, conv, infer, want_sums=fused)
+            routes.append(route)
             if not kernel:
                 h = act(norm(h)).contiguous(memory_format=torch.channels_last)
-            elif fused_field_norm(norm):
-                h = norm.forward_elu(h)
+            elif fused:
+                h = norm.forward_elu(h, sums)
             elif infer and not norm.training:
                 h = ops.fourier_elu(h.contiguous(memory_format=torch.channels_last), *norm.folded())
             else:
                 h = FourierELUFunction.apply(norm(h))
-        return self._tail(h, mods[-1], self._bank(mods[-1], infer), infer)
+        out, route = self._tail(h, mods[-1], self._bank(mods[-1], infer), infer)
+        self.last_routes = routes + [route]
+        return out
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda and x.dtype == torch.float32:

@@ -1290,6 +1290,95 @@ def field_norm_elu_bwd_apply(x: torch.Tensor, dy: torch.Tensor, scale: torch.Ten
     return dx
 
 
+def steer_lift_supported(cin: int, k: int, fields: int) -> bool:
+    """Shapes the steerable lifting kernels take (eqa_steer_lift_supported): 1 or 3 input channels, k in {5, 7, 9}, 1..64 fields."""
+    return bool(_lib.load().eqa_steer_lift_supported(cin, k, fields))
+
+
+def steer_lift_layout(cin: int, k: int, fields: int) -> Tuple[int, int, int, int]:
+    """(groups, blocks per wave, steps, padded filter-row floats) of the packed operand (csrc/steer_lift.hip, file header): the
+    ceil(9 fields / 16) 16-channel blocks in groups of at most 3; a filter row of k cin floats padded to whole 4-tap steps."""
+    nblk = (FOURIER_FIELD_DIM * fields + 15) // 16
+    groups = (nblk + 2) // 3
+    rwp = (k * cin + 3) // 4 * 4
+    return groups, (nblk + groups - 1) // groups, k * (rwp // 4), rwp
+
+
+def pack_steer_lift_weights(bank: torch.Tensor) -> torch.Tensor:
+    """(9 fields, Cin, K, K) bank -> (groups, bpw, steps, 64) operand of eqa_steer_lift_fwd, in torch ops on the bank's device:
+    wpk[g][b][s][lane] = bank[16 (g bpw + b) + (lane & 15)][ci][ky][kx] with ky = s // (rwp/4), column 4 (s % (rwp/4)) + (lane >> 4)
+    = kx Cin + ci; zero for the columns past K Cin and the channels past 9 fields."""
+    C9, Cin, K, K2 = bank.shape
+    if K != K2 or C9 % FOURIER_FIELD_DIM:
+        raise ValueError(f"pack_steer_lift_weights: a (9 fields, Cin, K, K) bank is expected, got {tuple(bank.shape)}")
+    groups, bpw, steps, rwp = steer_lift_layout(Cin, K, C9 // FOURIER_FIELD_DIM)
+    rows = bank.detach().float().permute(0, 2, 3, 1).reshape(C9, K, K * Cin)       # [co][ky][kx Cin + ci]
+    padded = rows.new_zeros(groups * bpw * 16, K, rwp)
+    padded[:C9, :, :K * Cin] = rows
+    # [g][b][li][ky][cs][q] -> [g][b][ky][cs][q][li]
+    t = padded.view(groups, bpw, 16, K, rwp // 4, 4).permute(0, 1, 3, 4, 5, 2)
+    return t.reshape(groups, bpw, steps, 64).contiguous()
+
+
+def _steer_lift_map(t: torch.Tensor, name: str, what: str) -> torch.Tensor:
+    """t as the kernels read it: fp32, on the device, channels-last (for one channel a contiguous NCHW map is the same memory)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+        raise RuntimeError(f"{what} expects {name} as a 4-d fp32 tensor on the device")
+    if not (t.is_contiguous(memory_format=torch.channels_last) or (t.shape[1] == 1 and t.is_contiguous())):
+        raise RuntimeError(f"{what} expects {name} channels-last")
+    return t
+
+
+def steer_lift(x: torch.Tensor, wpk: torch.Tensor, k: int, fields: int, with_stats: bool = False):
+    """y:(B, 9 fields, H-k+1, W-k+1) channels-last = conv2d(x, bank) for wpk = pack_steer_lift_weights(bank) (eqa_steer_lift_fwd).
+    with_stats: also the (fields, 6) fp64 sums of `field_norm_stats(y).sum(0)` (sum a_0, sum a_0^2, sum (Re^2 + Im^2) of
+    c_1..c_4), taken from the values on their way out of the kernel and folded here in torch ops on the device; else None."""
+    lib = _lib.load()
+    x = _steer_lift_map(x, "x", "steer_lift")
+    wpk = _need(wpk, "wpk")
+    B, Cin, H, W = x.shape
+    if not steer_lift_supported(Cin, k, fields) or H < k or W < k:
+        raise _lib.EqaLibraryError(f"steer_lift: (Cin, k, fields, H, W) = {(Cin, k, fields, H, W)} is not a shape the kernel takes")
+    if wpk.numel() != lib.eqa_steer_lift_packed_floats(Cin, k, fields):
+        raise ValueError("steer_lift: wpk is not pack_steer_lift_weights of a bank of this shape")
+    C9 = FOURIER_FIELD_DIM * fields
+    y = torch.empty((B, C9, H - k + 1, W - k + 1), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    part = torch.empty((int(lib.eqa_steer_lift_stat_rows(fields)), C9, 2), dtype=torch.float64, device=x.device) if with_stats else None
+    if B == 0:
+        return y, (torch.zeros((fields, 6), dtype=torch.float64, device=x.device) if with_stats else None)
+    with torch.cuda.device(x.device), _timed("steer_lift"):
+        st = lib.eqa_steer_lift_fwd(x.data_ptr(), wpk.data_ptr(), y.data_ptr(), part.data_ptr() if with_stats else None, B, H, W, Cin,
+                                    k, fields, _stream())
+    _lib.check(st, "eqa_steer_lift_fwd")
+    if not with_stats:
+        return y, None
+    ch = part.sum(0).view(fields, FOURIER_FIELD_DIM, 2)                     # per channel: sum, sum of squares
+    sq = ch[:, 1:, 1].reshape(fields, 4, 2).sum(2)                          # Re^2 + Im^2 of c_1..c_4
+    return y, torch.cat([ch[:, 0, :], sq], dim=1)
+
+
+def steer_lift_wgrad(x: torch.Tensor, dy: torch.Tensor, k: int) -> torch.Tensor:
+    """d loss / d bank (9 fields, Cin, k, k) of `steer_lift` from x and channels-last dy, deterministic (eqa_steer_lift_wgrad)."""
+    lib = _lib.load()
+    x = _steer_lift_map(x, "x", "steer_lift_wgrad")
+    dy = _steer_lift_map(dy, "dy", "steer_lift_wgrad")
+    B, Cin, H, W = x.shape
+    C9 = dy.shape[1]
+    fields = C9 // FOURIER_FIELD_DIM
+    if C9 % FOURIER_FIELD_DIM or tuple(dy.shape) != (B, C9, H - k + 1, W - k + 1):
+        raise RuntimeError("steer_lift_wgrad: dy does not match x and the kernel size")
+    if not steer_lift_supported(Cin, k, fields):
+        raise _lib.EqaLibraryError(f"steer_lift_wgrad: (Cin, k, fields) = {(Cin, k, fields)} is not a shape the kernel takes")
+    if B == 0:
+        return torch.zeros((C9, Cin, k, k), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(lib.eqa_steer_lift_wgrad_workspace_bytes(Cin, k, fields), 16) // 4, dtype=torch.float32, device=x.device)
+    dbank = torch.empty((C9, Cin, k, k), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("steer_lift_wgrad"):
+        st = lib.eqa_steer_lift_wgrad(x.data_ptr(), dy.data_ptr(), ws.data_ptr(), dbank.data_ptr(), B, H, W, Cin, k, fields, _stream())
+    _lib.check(st, "eqa_steer_lift_wgrad")
+    return dbank
+
+
 VNDEEPSETS_WIDTHS = (8, 16, 32)  # hidden widths the kernels are compiled for (csrc/nbody.hip); the caller zero-pads others
 VNDEEPSETS_MAX_HIDDEN = 32
 VNDEEPSETS_MAX_LAYERS = 8         # == kMaxLayers

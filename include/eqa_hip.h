@@ -952,6 +952,35 @@ long long eqa_gconv1x1_wgrad_workspace_bytes(long long P, int Cin, int Cout);
 int eqa_gconv1x1_wgrad(const float* x, const float* dz, float* dW, float* dbias, void* workspace, long long P, int Cin, int Cout,
                        void* stream);
 
+/*
+ * The first layer of ESCNNSteerableNetwork (csrc/steer_lift.hip; reference network: escnn_networks.py:178-186, the first R2Conv):
+ * a dense real convolution of a channels-last fp32 map x:(nimg, Cin, H, W) with a bank (9 fields, Cin, K, K), stride 1, no padding,
+ * no bias, onto y:(nimg, 9 fields, H-K+1, W-K+1) channels-last, on the fp32 matrix instruction at 16-channel granularity.
+ *   eqa_steer_lift_supported       Cin in {1, 3}, K in {5, 7, 9}, 1 <= fields <= eqa_field_norm_max_fields()
+ *   eqa_steer_lift_packed_floats   floats of the packed weight operand wpk (layout: the header of csrc/steer_lift.hip;
+ *                                  ops.pack_steer_lift_weights builds it); 0 for an unsupported shape
+ *   eqa_steer_lift_stat_rows       rows of `part` for this field count (< 0: the error code)
+ *   eqa_steer_lift_fwd             part == NULL: y only.  Otherwise part:(rows, 9 fields, 2) fp64 also receives, per row and
+ *                                  channel, the sum and the sum of squares of the values stored to y, fp64 from the first add
+ *                                  (squares of converted values: exact terms), every row written, no atomics: two launches give
+ *                                  the same bits.  Summed over the rows and folded per field they are the six sums of
+ *                                  eqa_field_norm_stats on y.  y is the same with and without part.
+ *   eqa_steer_lift_wgrad           dbank:(9 fields, Cin, K, K) fp32 = sum over (n, oy, ox) of dy[n,oy,ox,co] x[n,oy+ky,ox+kx,ci],
+ *                                  per-wave partials in workspace (eqa_steer_lift_wgrad_workspace_bytes) added in a fixed order
+ * Checks, all before any launch: a shape outside the predicate, H < K or W < K, more than 2^31 - 1 tiles or input floats, y or dy
+ * off its 16-byte line: EQA_ERR_UNSUPPORTED (the shape checks before any pointer is looked at); nimg < 0, H or W <= 0, NULL x /
+ * wpk / y / dy / workspace / dbank: EQA_ERR_INVALID_ARG; nimg == 0: EQA_OK, nothing launched.  Added without touching an existing
+ * signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_steer_lift_supported(int Cin, int K, int fields);
+int64_t eqa_steer_lift_packed_floats(int Cin, int K, int fields);
+long long eqa_steer_lift_stat_rows(int fields);
+int eqa_steer_lift_fwd(const float* x, const float* wpk, float* y, double* part, int nimg, int H, int W, int Cin, int K, int fields,
+                       void* stream);
+int64_t eqa_steer_lift_wgrad_workspace_bytes(int Cin, int K, int fields);
+int eqa_steer_lift_wgrad(const float* x, const float* dy, void* workspace, float* dbank, int nimg, int H, int W, int Cin, int K,
+                         int fields, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

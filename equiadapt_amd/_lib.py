@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("EQA_LIB") or os.path.join(CSRC, "libeqa_hip.so")  # EQA_LIB: A/B a variant build
-SOURCES = [os.path.join(CSRC, f) for f in ("group_action.hip", "crop_resize.hip", "nearest_action.hip", "pooling.hip", "batchnorm.hip", "winograd.hip", "lift_conv.hip", "lift_conv_wide.hip", "lift_wgrad.hip", "pointcloud.hip", "vnsmall_fwd.hip", "nbody_frame.hip", "vnsmall_train.hip", "vnsmall_tail.hip", "fftconv.hip", "fft_filter.hip", "lift_fft.hip", "cgemm3m.hip", "cgemm3m_bf16.hip", "smallconv.hip", "planegemm.hip", "convnet_train.hip", "fourier_act.hip", "field_norm.hip", "nbody.hip", "vn_act.hip", "gconv1x1.hip", "steer_lift.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("group_action.hip", "crop_resize.hip", "nearest_action.hip", "pooling.hip", "batchnorm.hip", "winograd.hip", "lift_conv.hip", "lift_conv_wide.hip", "lift_wgrad.hip", "pointcloud.hip", "vnsmall_fwd.hip", "nbody_frame.hip", "vnsmall_train.hip", "vnsmall_tail.hip", "fftconv.hip", "fft_filter.hip", "lift_fft.hip", "cgemm3m.hip", "cgemm3m_bf16.hip", "cgemm3m_c16.hip", "smallconv.hip", "planegemm.hip", "convnet_train.hip", "fourier_act.hip", "field_norm.hip", "nbody.hip", "vn_act.hip", "gconv1x1.hip", "steer_lift.hip")]
 HEADERS = [os.path.join(CSRC, "eqa_common.hpp"), os.path.join(CSRC, "vn_common.hpp"), os.path.join(CSRC, "fourier_field.hpp"), os.path.join(CSRC, "fft48.inc"), os.path.join(CSRC, "fft_common.inc"), os.path.join(CSRC, "cgemm3m_common.inc")]
 INCLUDE = os.path.join(ROOT, "include")
 
@@ -119,6 +119,13 @@ SIGNATURES = {
     "eqa_fft48k5_cgemm3m_f16x2": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, _int, _vp, _int, ctypes.c_float, _vp]),
     "eqa_fft48k5_wgrad3m_supported": (_int, [_int, _int]),
     "eqa_fft48k5_wgrad3m": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, _int, _vp]),
+    "eqa_fft48_cgemm3m_c16_supported": (_int, [_int, _int]),
+    "eqa_fft48_spectra3m_c16_floats": (ctypes.c_int64, [_int, _int]),
+    "eqa_fft48k5_filter_spectra3m_c16": (_int, [_vp, _vp, _int, _int, _int, _vp]),
+    "eqa_fft48_filter_spectra3m_c16": (_int, [_vp, _vp, _int, _int, _int, _int, _vp]),
+    "eqa_fft48_cgemm3m_c16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, _int, _vp]),
+    "eqa_fft48_wgrad3m_c16_supported": (_int, [_int, _int]),
+    "eqa_fft48_wgrad3m_c16": (_int, [_vp, _vp, _vp, ctypes.c_int64, _int, _int, _vp]),
     "eqa_fft48k5_group": (_int, [_int, _int]),
     "eqa_fft48k5_workspace_bytes": (ctypes.c_int64, [_int] * 4),
     "eqa_fft48k5_input": (_int, [_vp, _vp, _vp, _vp] + [_int] * 5 + [_vp]),

@@ -14,7 +14,12 @@ namespace {
 // 48-entry table): 0.3 ms for 256 x 256 filters, against 13.6 ms for the same through torch.fft + concatenations -- cheap
 // enough to run every training step.
 // `sgn` = +1: the correlation form above (forward pass); -1: FFT(filter) itself, for the convolution of the input gradient.
-template <int KS>
+// C16: the same thread, the same sums, another store -- the operand of cgemm3m_c16.hip, B3 (F, Cin/16, n_ct = ceil(Cout/32), 3 [Br | Bi |
+// Br + Bi], 2 [b], 64 [lane = 32 h + j], 4 [t]) with input channel 16 s + 8 b + 4 h + t, output channel 32 c + j and the columns
+// Cout .. 32 n_ct - 1 zero (G is then n_ct).  It is this kernel and not fft48_filter_spectra3m_kernel below so that Br, Bi are the
+// floats of B bit for bit: the two kernels' fp64 sums are contracted into fused multiply-adds differently and differ by an ulp in a
+// few entries per 10^7 (heavily cancelled ones).  Br + Bi: the correctly rounded sum of the two stored floats, as below.
+template <int KS, bool C16 = false>
 __global__ __launch_bounds__(kThreads) void fft48_filter_spectra_kernel(const float* __restrict__ bank, float* __restrict__ B, int Cout,
                                                                        int Cin, int G, float sgn) {
   __shared__ double tw_c[kFftN], tw_s[kFftN];
@@ -26,11 +31,19 @@ __global__ __launch_bounds__(kThreads) void fft48_filter_spectra_kernel(const fl
   __syncthreads();
   const int co = blockIdx.y * kThreads + threadIdx.x;
   const int ci = blockIdx.x;
+  // C16: element (part 0, this ci, this co) of frequency 0; parts are 512 floats apart, frequencies f3
+  const size_t f3 = C16 ? (size_t)Cin * 32 * G * 3 : 0;
+  float* o3 = C16 ? B + ((((size_t)(ci / 16) * G + co / 32) * 3 * 2 + (ci % 16) / 8) * 64 + 32 * ((ci % 8) / 4) + co % 32) * 4 + ci % 4 : nullptr;
+  if (C16 && co >= Cout) {
+    if (co < 32 * G)
+      for (int f = 0; f < kFftF; ++f) o3[f * f3] = o3[f * f3 + 512] = o3[f * f3 + 1024] = 0.f;
+    return;
+  }
   if (co >= Cout) return;
   double w[KS * KS];
 #pragma unroll
   for (int i = 0; i < KS * KS; ++i) w[i] = bank[((size_t)co * Cin + ci) * (KS * KS) + i];
-  const int r0 = (ci / G) * 2 * G + ci % G, r1 = r0 + G;
+  const int r0 = C16 ? 0 : (ci / G) * 2 * G + ci % G, r1 = r0 + G;
   const size_t fstride = (size_t)2 * Cin * 2 * Cout;
   float2* o0 = reinterpret_cast<float2*>(B + (size_t)r0 * 2 * Cout) + co;
   float2* o1 = reinterpret_cast<float2*>(B + (size_t)r1 * 2 * Cout) + co;
@@ -61,6 +74,13 @@ __global__ __launch_bounds__(kThreads) void fft48_filter_spectra_kernel(const fl
         bi += c * si[u] + sn * sr[u];
       }
       const float fr = (float)(br * inv), fi = sgn * (float)(bi * inv);
+      if (C16) {
+        float* of = o3 + (size_t)(f0 + ky * fstep) * f3;
+        of[0] = fr;
+        of[512] = fi;
+        of[1024] = (float)((double)fr + (double)fi);
+        continue;
+      }
       const size_t f = (size_t)(f0 + ky * fstep) * (fstride / 2);  // in float2
       o0[f] = make_float2(fr, fi);
       o1[f] = make_float2(-fi, fr);
@@ -304,6 +324,12 @@ struct FftFilterK {
                        correlate ? 1.0f : -1.0f);
     return launch_status();
   }
+  static int spectra3m_c16(const float* bank, float* B3, int Cout, int Cin, int correlate, hipStream_t st) {
+    const int n_ct = (Cout + 31) / 32;
+    hipLaunchKernelGGL((fft48_filter_spectra_kernel<KS, true>), grid(32 * n_ct, Cin), dim3(kThreads), 0, st, bank, B3, Cout, Cin, n_ct,
+                       correlate ? 1.0f : -1.0f);
+    return launch_status();
+  }
   static int spectra3m(const float* bank, float* B3, int Cout, int Cin, int correlate, hipStream_t st) {
     hipLaunchKernelGGL(fft48_filter_spectra3m_kernel<KS>, grid(Cout, Cin / 4, kFftH), dim3(kThreads), 0, st, bank, B3, Cout, Cin,
                        correlate ? 1.0f : -1.0f);
@@ -331,6 +357,10 @@ int spectra3m_args(const float* bank, const float* B3, int Cout, int Cin) {
   if (!bank || !B3 || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
   return (((uintptr_t)B3 & 15) || Cin % 32 || Cout % 64 || Cin / 4 > 65535) ? EQA_ERR_UNSUPPORTED : EQA_OK;
 }
+int spectra3m_c16_args(const float* bank, const float* B3, int Cout, int Cin) {
+  if (!bank || !B3 || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
+  return (((uintptr_t)B3 & 15) || Cin % 16 || Cout % 16 || Cin > 65535) ? EQA_ERR_UNSUPPORTED : EQA_OK;
+}
 int filter_grad_args(const float* D, const float* dbank, int Cout, int Cin, bool packed) {
   if (!D || !dbank || Cout <= 0 || Cin <= 0) return EQA_ERR_INVALID_ARG;
   return (Cin > 65535 || (packed && (Cin % kFusCh || Cout % kFusCh))) ? EQA_ERR_UNSUPPORTED : EQA_OK;
@@ -355,6 +385,11 @@ int eqa_fft48k5_filter_spectra3m(const float* bank, float* B3, int Cout, int Cin
   return FftFilterK<5>::spectra3m(bank, B3, Cout, Cin, correlate, (hipStream_t)stream);
 }
 
+int eqa_fft48k5_filter_spectra3m_c16(const float* bank, float* B3, int Cout, int Cin, int correlate, void* stream) {
+  if (const int rc = spectra3m_c16_args(bank, B3, Cout, Cin)) return rc;
+  return FftFilterK<5>::spectra3m_c16(bank, B3, Cout, Cin, correlate, (hipStream_t)stream);
+}
+
 int eqa_fft48k5_filter_grad(const float* D, float* dbank, int Cout, int Cin, void* stream) {
   if (const int rc = filter_grad_args(D, dbank, Cout, Cin, false)) return rc;
   return FftFilterK<5>::filter_grad<false>(D, dbank, Cout, Cin, /*row_form=*/false, (hipStream_t)stream);
@@ -373,6 +408,11 @@ int eqa_fft48_filter_spectra(const float* bank, float* B, int Cout, int Cin, int
 int eqa_fft48_filter_spectra3m(const float* bank, float* B3, int Cout, int Cin, int ksize, int correlate, void* stream) {
   if (const int rc = spectra3m_args(bank, B3, Cout, Cin)) return rc;
   EQA_FFT_K(ksize, FftFilterK, K_::spectra3m(bank, B3, Cout, Cin, correlate, (hipStream_t)stream));
+}
+
+int eqa_fft48_filter_spectra3m_c16(const float* bank, float* B3, int Cout, int Cin, int ksize, int correlate, void* stream) {
+  if (const int rc = spectra3m_c16_args(bank, B3, Cout, Cin)) return rc;
+  EQA_FFT_K(ksize, FftFilterK, K_::spectra3m_c16(bank, B3, Cout, Cin, correlate, (hipStream_t)stream));
 }
 
 int eqa_fft48_filter_grad(const float* D, float* dbank, int Cout, int Cin, int ksize, int packed, void* stream) {

@@ -24,7 +24,8 @@ ENABLED = os.environ.get("EQA_CONV5_FFT", "1") != "0"
 MIN_TILES = int(os.environ.get("EQA_FFT_MIN_TILES", "32"))
 TRAIN_FORWARD = os.environ.get("EQA_FFT_TRAIN", "1") != "0"     # forward pass of winograd.Conv5x5Function through this path
 # The per-frequency channel contraction: "3m" = the hand-written complex GEMM on the fp32 MFMA in the 3-multiplication form
-# (eqa_fft48k5_cgemm3m; channel counts it takes: Cin % 32 == 0, Cout % 64 == 0), "lib" = the library's real batched GEMM.
+# (eqa_fft48k5_cgemm3m; channel counts it takes: Cin % 32 == 0, Cout % 64 == 0; other multiples of 16: eqa_fft48_cgemm3m_c16, see
+# GEMM_C16 below), "lib" = the library's real batched GEMM.
 GEMM = os.environ.get("EQA_FFT_GEMM", "3m")
 # How the hand-written GEMM multiplies: "f32" = the fp32 matrix instruction; "9" / "6" = every fp32 operand split exactly into three
 # bf16 pieces and that many piece products on the bf16 matrix cores (eqa_fft48k5_cgemm3m_bf16x3: 9 = every product, the same
@@ -44,6 +45,12 @@ AUTO_MIN_CIN = int(os.environ.get("EQA_FFT_GEMM_AUTO_MIN_CIN", "128"))
 AUTO_MIN_CIN_H3 = int(os.environ.get("EQA_FFT_GEMM_AUTO_MIN_CIN_H3", "64"))
 DCMAX_SLOTS = 256       # EQA_LIFT5_DCMAX_SLOTS (include/eqa_hip.h)
 LAST_FORM = None        # the form the most recent `contract` on the hand-written GEMM ran in (bench.py reports it)
+# Channel counts the kernels above do not take but that are multiples of 16 (144 = 16 fields x 9 of the steerable network, 288, 48,
+# 80): the same 3-multiplication arithmetic on 64 x 32 wave tiles (eqa_fft48_cgemm3m_c16) and, for the filter gradient, 32 x 32
+# channel tiles (eqa_fft48_wgrad3m_c16).  EQA_FFT_GEMM_C16=0: the library's real batched GEMM for both, as before they existed.
+GEMM_C16 = os.environ.get("EQA_FFT_GEMM_C16", "1") != "0"
+LAST_CONTRACTION = None   # which contraction the most recent `contract` ran: "3m" (eqa_fft48k5_cgemm3m*), "c16", "lib" (torch.bmm)
+LAST_WGRAD = None         # ... and the most recent `filter_grad_k`: "3m" (eqa_fft48k5_wgrad3m), "c16", "lib"
 
 
 def f16_form_takes(cin: int, cout: int) -> bool:
@@ -107,6 +114,49 @@ def gemm3m_supported(cin: int, cout: int) -> bool:
     return GEMM == "3m" and bool(_lib.load().eqa_fft48k5_cgemm3m_supported(cin, cout))
 
 
+class Spectra3MC16:
+    """Filter spectra in the operand order of eqa_fft48_cgemm3m_c16: ``data`` is the flat fp32 buffer
+    (F, Cin/16, ceil(Cout/32), 3 [Br | Bi | Br + Bi], 2, 64, 4) with the columns beyond Cout zero (include/eqa_hip.h).  fp32 only: the
+    bf16 / fp16 piece forms do not exist for these channel counts."""
+
+    __slots__ = ("data", "cin", "cout")
+
+    def __init__(self, data: torch.Tensor, cin: int, cout: int):
+        self.data, self.cin, self.cout = data, cin, cout
+
+    def unpack(self, pad: bool = False):
+        """(Br, Bi, Bs) as (F, Cin, Cout) tensors (``pad``: (F, Cin, 32 ceil(Cout/32)), the padding columns included)."""
+        nct = (self.cout + 31) // 32
+        t = self.data.view(F, self.cin // 16, nct, 3, 2, 2, 32, 4)             # (f, s, c, part, b, h, j, t)
+        t = t.permute(3, 0, 1, 4, 5, 7, 2, 6).reshape(3, F, self.cin, nct * 32)   # k = 16 s + 8 b + 4 h + t; column 32 c + j
+        if not pad:
+            t = t[..., :self.cout]
+        return t[0], t[1], t[2]
+
+
+def gemm3m_c16_supported(cin: int, cout: int) -> bool:
+    """The 16-multiple contraction takes what the kernels above leave to the library."""
+    return (GEMM == "3m" and GEMM_C16 and not gemm3m_supported(cin, cout)
+            and bool(_lib.load().eqa_fft48_cgemm3m_c16_supported(cin, cout)))
+
+
+def filter_spectra3m_c16(bank: torch.Tensor, correlate: bool = True) -> Spectra3MC16:
+    """(Cout, Cin, k, k) fp32 device bank -> the spectra of `filter_spectra` / `spectra_for_k`, laid out for eqa_fft48_cgemm3m_c16."""
+    lib = _lib.load()
+    Cout, Cin, k = bank.shape[0], bank.shape[1], bank.shape[-1]
+    if not (bank.is_cuda and bank.dtype == torch.float32 and lib.eqa_fft48_cgemm3m_c16_supported(Cin, Cout)):
+        raise RuntimeError("filter_spectra3m_c16: fp32 device bank with Cin % 16 == 0 and Cout % 16 == 0 expected")
+    B3 = torch.empty(lib.eqa_fft48_spectra3m_c16_floats(Cin, Cout), dtype=torch.float32, device=bank.device)
+    with torch.cuda.device(bank.device):
+        if k == 5:
+            _lib.check(lib.eqa_fft48k5_filter_spectra3m_c16(bank.contiguous().data_ptr(), B3.data_ptr(), Cout, Cin, int(correlate),
+                                                            ops._stream()), "eqa_fft48k5_filter_spectra3m_c16")
+        else:
+            _lib.check(lib.eqa_fft48_filter_spectra3m_c16(bank.contiguous().data_ptr(), B3.data_ptr(), Cout, Cin, k, int(correlate),
+                                                          ops._stream()), "eqa_fft48_filter_spectra3m_c16")
+    return Spectra3MC16(B3, Cin, Cout)
+
+
 def filter_spectra3m(bank: torch.Tensor, correlate: bool = True) -> Spectra3M:
     """(Cout, Cin, 5, 5) device bank -> the same spectra as `filter_spectra`, laid out for the 3-multiplication complex GEMM."""
     lib = _lib.load()
@@ -126,6 +176,8 @@ def spectra_for(bank: torch.Tensor, correlate: bool = True):
     Cout, Cin = bank.shape[:2]
     if bank.is_cuda and bank.dtype == torch.float32 and gemm3m_supported(Cin, Cout):
         return filter_spectra3m(bank, correlate)
+    if bank.is_cuda and bank.dtype == torch.float32 and gemm3m_c16_supported(Cin, Cout):
+        return filter_spectra3m_c16(bank, correlate)
     return filter_spectra(bank, correlate=correlate)
 
 
@@ -133,11 +185,20 @@ def contract(V: torch.Tensor, B, M: int, vbound: Optional[torch.Tensor] = None) 
     """Mo[f] = V[f] . B[f] for every stored frequency: V (F, M, 2Cin) view of a pitched buffer -> Mo (F, M, 2Cout) likewise.
     ``vbound``: a device fp32 tensor whose maximum bounds every |Re|, |Im| of V (the producer's DC bins) -- admits the fp16 form."""
     dev = V.device
+    global LAST_FORM, LAST_CONTRACTION
+    if isinstance(B, Spectra3MC16):
+        lib = _lib.load()
+        assert V.shape[2] == 2 * B.cin and V.stride(1) == 2 * B.cin and V.stride(0) == lib.eqa_fft48k5_tile_pitch(M) * 2 * B.cin
+        Mo = spectra_buffer(M, 2 * B.cout, dev)
+        LAST_CONTRACTION = "c16"
+        _lib.check(lib.eqa_fft48_cgemm3m_c16(V.data_ptr(), B.data.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, ops._stream()),
+                   "eqa_fft48_cgemm3m_c16")
+        return Mo
     if isinstance(B, Spectra3M):
         lib = _lib.load()
         assert V.shape[2] == 2 * B.cin and V.stride(1) == 2 * B.cin and V.stride(0) == lib.eqa_fft48k5_tile_pitch(M) * 2 * B.cin
         Mo = spectra_buffer(M, 2 * B.cout, dev)
-        global LAST_FORM
+        LAST_CONTRACTION = "3m"
         form = LAST_FORM = gemm_form(B.cin, B.cout, vbound is not None)
         if form == "h3":
             bh, b_scale = B.pieces_f16()
@@ -152,6 +213,7 @@ def contract(V: torch.Tensor, B, M: int, vbound: Optional[torch.Tensor] = None) 
         _lib.check(lib.eqa_fft48k5_cgemm3m(V.data_ptr(), B.data.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout,
                                            ops._stream()), "eqa_fft48k5_cgemm3m")
         return Mo
+    LAST_CONTRACTION = "lib"
     return torch.bmm(V, B, out=spectra_buffer(M, B.shape[2], dev))
 
 
@@ -471,6 +533,8 @@ def spectra_for_k(bank: torch.Tensor, correlate: bool = True):
             _lib.check(lib.eqa_fft48_filter_spectra3m(bank.contiguous().data_ptr(), B3.data_ptr(), Cout, Cin, k, int(correlate), st),
                        "eqa_fft48_filter_spectra3m")
             return Spectra3M(B3, Cin, Cout)
+        if gemm3m_c16_supported(Cin, Cout):
+            return filter_spectra3m_c16(bank, correlate)
         B = torch.empty((F, 2 * Cin, 2 * Cout), dtype=torch.float32, device=bank.device)
         _lib.check(lib.eqa_fft48_filter_spectra(bank.contiguous().data_ptr(), B.data_ptr(), Cout, Cin, k, int(correlate), st),
                    "eqa_fft48_filter_spectra")
@@ -488,7 +552,7 @@ def conv_kxk(x: torch.Tensor, B, k: int, bias: Optional[torch.Tensor], relu: boo
     no bias / activation; the caller checks ``output_stats_supported``)."""
     lib = _lib.load()
     nimg, Cin, H, W = x.shape
-    if isinstance(B, Spectra3M):
+    if isinstance(B, (Spectra3M, Spectra3MC16)):
         Cout = B.cout
         assert B.cin == Cin
     else:
@@ -561,6 +625,19 @@ def grad_spectra(dy: torch.Tensor, k: int = 5) -> torch.Tensor:
     return G
 
 
+def wgrad_c16_admitted(M: int, cin: int, cout: int) -> bool:
+    """Does the filter gradient's contraction over M tiles run eqa_fft48_wgrad3m_c16 rather than the library's GEMM?  Its 32 x 32
+    channel tiles do pad32(cin) pad32(cout) / (cin cout) times the work, and the three-product form saves a quarter: admitted where
+    that ratio is below 4/3 (96, 112, 144, 288 channels: 1.09 - 1.3 x the library at M = 1024, up to 3.9 x below).  With more padding
+    (48 x 48, 48 x 80, 80 x 80: 1.44 - 1.78) it ties with or loses to the library from 512 tiles up and wins only where the library's
+    batched GEMM is far from its rate: admitted up to 72 tiles from 48 channels (16 x 16 at M = 1024: 0.105 against 0.067 ms).
+    Measured: DESIGN.md section 1, profiles/cgemm3m_c16/."""
+    if not (GEMM_C16 and _lib.load().eqa_fft48_wgrad3m_c16_supported(cin, cout)):
+        return False
+    pad = (-(-cin // 32) * 32) * (-(-cout // 32) * 32)
+    return 3 * pad < 4 * cin * cout or (M <= 72 and min(cin, cout) >= 48)
+
+
 def filter_grad_k(V: torch.Tensor, dy: torch.Tensor, cin: int, k: int, G: Optional[torch.Tensor] = None) -> torch.Tensor:
     """d loss / d filter bank (Cout, Cin, k, k) of y = conv2d(x, bank) from V = the spectra of x's tiles (``keep_V`` of the
     forward pass) and the output gradient dy (channels-last): spectra of the disjoint gradient tiles, one batched GEMM
@@ -577,11 +654,18 @@ def filter_grad_k(V: torch.Tensor, dy: torch.Tensor, cin: int, k: int, G: Option
         G = grad_spectra(dy, k)
     dbank = torch.empty((Cout, cin, k, k), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        packed = GEMM == "3m" and lib.eqa_fft48k5_wgrad3m_supported(cin, Cout) and os.environ.get("EQA_FFT_WGRAD3M", "1") != "0"
+        global LAST_WGRAD
+        wgrad3m = GEMM == "3m" and os.environ.get("EQA_FFT_WGRAD3M", "1") != "0"
+        LAST_WGRAD = ("3m" if wgrad3m and lib.eqa_fft48k5_wgrad3m_supported(cin, Cout) else
+                      "c16" if wgrad3m and wgrad_c16_admitted(M, cin, Cout) else "lib")
+        packed = LAST_WGRAD != "lib"
         if packed:
             # the contraction over the tiles in the 3-multiplication form on the fp32 MFMA (the library's real GEMM: 4 products)
             D = torch.empty((F, cin, 2, Cout), dtype=torch.float32, device=dev)      # Dr | Di per input channel
-            _lib.check(lib.eqa_fft48k5_wgrad3m(V.data_ptr(), G.data_ptr(), D.data_ptr(), M, cin, Cout, st), "eqa_fft48k5_wgrad3m")
+            if LAST_WGRAD == "3m":
+                _lib.check(lib.eqa_fft48k5_wgrad3m(V.data_ptr(), G.data_ptr(), D.data_ptr(), M, cin, Cout, st), "eqa_fft48k5_wgrad3m")
+            else:
+                _lib.check(lib.eqa_fft48_wgrad3m_c16(V.data_ptr(), G.data_ptr(), D.data_ptr(), M, cin, Cout, st), "eqa_fft48_wgrad3m_c16")
         else:
             D = torch.bmm(V.transpose(1, 2), G)                   # (F, 2 Cin, 2 Cout)
         if k != 5:                                                # (one entry point, told which D it reads)

@@ -556,6 +556,27 @@ int eqa_fft48k5_cgemm3m_f16x2(const float* V, const void* Bh, float* Mo, int64_t
 int eqa_fft48k5_wgrad3m_supported(int Cin, int Cout);
 int eqa_fft48k5_wgrad3m(const float* V, const float* G, float* D, int64_t M, int Cin, int Cout, void* stream);
 int eqa_fft48k5_filter_grad3m(const float* D, float* dbank, int Cout, int Cin, void* stream);
+/* Both contractions for channel counts that are multiples of 16 but not of the above (csrc/cgemm3m_c16.hip): 144 = 16 fields x 9 of
+ * the steerable network's hidden layers (escnn_networks.py through R2Conv), 288, 48, 80, ...  The same 3-multiplication arithmetic on
+ * the fp32 matrix instruction with fp32 accumulation; any kernel size (the contractions do not depend on it).  Deterministic.
+ *   eqa_fft48_cgemm3m_c16_supported   1 when Cin % 16 == 0 and Cout % 16 == 0 (both > 0).
+ *   eqa_fft48_spectra3m_c16_floats    floats of B3 = F * Cin * 32 ceil(Cout / 32) * 3; 0: shape not taken.
+ *   eqa_fft48[k5]_filter_spectra3m_c16  bank:(Cout,Cin,k,k) -> B3:(F, Cin/16, ceil(Cout/32), 3 [Br|Bi|Br+Bi], 2, 64 [lane = 32 h + j],
+ *                                     4 [t]): input channel 16 s + 8 b + 4 h + t, output channel 32 c + j -- the fragment order of
+ *                                     eqa_fft48k5_filter_spectra3m with the columns padded to whole 32-column tiles.  Br, Bi are the
+ *                                     values of eqa_fft48[k5]_filter_spectra, Br + Bi their correctly rounded sum, columns >= Cout 0.
+ *   eqa_fft48_cgemm3m_c16             V:(F, pitch(M), 2Cin) rows [Re x 16 | Im x 16] per 16 channels, B3 -> Mo:(F, pitch(M), 2Cout)
+ *                                     interleaved complex; rows >= M and the padding columns are neither written nor stored.
+ *   eqa_fft48_wgrad3m_c16             V:(F, pitch(M), 2Cin), G:(F, pitch(M), 2Cout) -> D3:(F, Cin, 2, Cout) as eqa_fft48k5_wgrad3m.
+ * Both contractions return EQA_ERR_INVALID_ARG for a null pointer or M < 0, EQA_ERR_UNSUPPORTED for other channel counts, pointers
+ * that are not 16-byte aligned or sizes whose buffer ranges exceed 31 bits, before any launch; M == 0: EQA_OK, nothing written. */
+int eqa_fft48_cgemm3m_c16_supported(int Cin, int Cout);
+int64_t eqa_fft48_spectra3m_c16_floats(int Cin, int Cout);
+int eqa_fft48k5_filter_spectra3m_c16(const float* bank, float* B3, int Cout, int Cin, int correlate, void* stream);
+int eqa_fft48_filter_spectra3m_c16(const float* bank, float* B3, int Cout, int Cin, int ksize, int correlate, void* stream);
+int eqa_fft48_cgemm3m_c16(const float* V, const float* B3, float* Mo, int64_t M, int Cin, int Cout, void* stream);
+int eqa_fft48_wgrad3m_c16_supported(int Cin, int Cout);
+int eqa_fft48_wgrad3m_c16(const float* V, const float* G, float* D, int64_t M, int Cin, int Cout, void* stream);
 int eqa_fft48k5_group(int C, int side);
 int64_t eqa_fft48k5_workspace_bytes(int nimg, int rows, int out_cols, int C);
 int eqa_fft48k5_input(const float* x, float* T, float* V, const float* in_bias, int in_relu, int nimg, int H, int W, int C,

@@ -38,6 +38,8 @@ SIGNATURES = {
     "eqa_group_action_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [_int] * 12 + [_vp]),
     "eqa_group_action_fwd_hint": (_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [_int] * 13 + [_vp]),
     "eqa_crop_resize_aa": (_int, [_vp] * 6 + [_int] * 9 + [_vp]),
+    "eqa_crop_resize_aa_nhwc_slots": (_int, [_int] * 10),
+    "eqa_crop_resize_aa_nhwc": (_int, [_vp] * 6 + [_int] * 10 + [_vp, _vp]),
     "eqa_mask_action_nearest": (_int, [_vp] * 5 + [_int] * 4 + [_vp]),
     "eqa_mask_action_nearest_planes": (_int, [_vp] * 5 + [_int] * 4 + [_vp]),
     "eqa_boxes_action": (_int, [_vp] * 5 + [_int, ctypes.c_float, _int, _vp]),
@@ -174,6 +176,8 @@ SIGNATURES = {
     "eqa_window_sums_nhwc": (_int, [_vp, _vp, _vp, _int, _vp, _vp] + [_int] * 5 + [_vp]),
     "eqa_window_sums_bwd_expand_nhwc": (_int, [_vp, _vp] + [_int] * 5 + [_vp]),
     "eqa_group_argmax": (_int, [_vp, _vp, _int, _int, _vp]),
+    "eqa_fft48k5_output_sums_partials": (_int, [_vp, _vp, _vp, _int, _vp] + [_int] * 5 + [_vp, _vp]),
+    "eqa_window_sums_tail": (_int, [_vp] * 8 + [_int] * 6 + [ctypes.c_double, ctypes.c_double, _vp]),
     "eqa_vnsmall_workspace_bytes": (ctypes.c_int64, [_int, _int]),
     "eqa_vnsmall_fwd": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp]),
     "eqa_vnsmall_canonicalize": (_int, [_vp] * 6 + [_int] * 4 + [_vp]),

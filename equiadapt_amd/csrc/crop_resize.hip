@@ -404,9 +404,214 @@ __global__ __launch_bounds__(kThreads) void crop_resize_aa_stream_kernel(const f
   }
 }
 
+// The staged kernel for a consumer that reads pixels, not planes (the fused lifting kernel: (B, H, W, C)), and that wants a bound on
+// |y| beside them (it scales its pixels under one).  A block owns a band of IMAGES, not of planes: it runs the staged kernel's two
+// passes for the C planes of an image in turn -- same tables, same taps, same order of additions, so every pixel has the bits the
+// planar kernel gives it; the next plane's rows are requested before this one's passes run from LDS, across image boundaries as
+// well -- keeps the band's C x BAND x OW results in registers and stores them as ONE contiguous run of BAND * OW * C floats (as a
+// planar result the consumer's .contiguous(channels_last) was a 28 MB permute per step at the headline, and the bound a second
+// pass over the same 28 MB).  The largest |y| a block has stored goes to slots[block]: no atomics, nothing to clear; fmaxf drops
+// a NaN and carries an infinity, as absmax_slots_kernel (lift_fft.hip) does.
+constexpr int kAaNhwcTrips = 6;   // results per thread and plane: BAND * OW <= 6 * 256 (16 rows of 96)
+
+// (the C x kAaNhwcTrips results on top of the staged kernel's 127 registers: three blocks per CU -- what the 45 KB of a 16-row band
+// admit anyway -- instead of four; at four, 42 registers of the headline's instance went to scratch)
+template <int K, int BAND, int NL, int C>
+__global__ __launch_bounds__(kThreads, (NL > 5 && K > 5) ? 2 : 3) void crop_resize_aa_nhwc_kernel(
+    const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ wx, const int32_t* __restrict__ x0,
+    const float* __restrict__ wy, const int32_t* __restrict__ y0, int nimg, int H, int W, int OH, int OW, int cap_rows, int xb, int xl,
+    float* __restrict__ slots) {
+  extern __shared__ __attribute__((aligned(16))) float aa_tmp[];  // as crop_resize_aa_staged_kernel
+  float* rows = aa_tmp;
+  float* tmp = aa_tmp + (size_t)cap_rows * xl;
+  float* tabw = tmp + (size_t)cap_rows * OW;
+  int* taby = reinterpret_cast<int*>(tabw + BAND * K);
+  __shared__ float s_max[kThreads / 64];
+  // grid (8, bands, image groups): the bands of one image on one XCD, as the planar kernel keeps the bands of a plane
+  const int r0 = blockIdx.y * BAND, r1 = min(r0 + BAND, OH);
+  const int nband = r1 - r0;
+  const int img0 = (int)(blockIdx.z * kXcd + blockIdx.x), img_step = (int)(gridDim.z * kXcd);
+  const int rows_par = kThreads / OW;   // >= 1: OW <= kThreads (the host checks)
+  const int ox = threadIdx.x % OW, rsub = threadIdx.x / OW;
+  const int xs_g = x0[ox];
+  float wv[K];
+  int xo[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    wv[j] = wx[ox * K + j];
+    xo[j] = min(xs_g - xb + j, xl - 1);
+  }
+  if ((int)threadIdx.x < nband * K) tabw[threadIdx.x] = wy[r0 * K + threadIdx.x];
+  const int ybeg = y0[r0];
+  if ((int)threadIdx.x < nband) taby[threadIdx.x] = y0[r0 + threadIdx.x] - ybeg;
+  const int yend = min(y0[r1 - 1] + K, H);
+  const int nrows = min(yend - ybeg, cap_rows);
+  const int nq = xl >> 2;
+  const int tq = threadIdx.x & 63, tr = threadIdx.x >> 6;
+  const bool prefetch = nq <= 64 && nrows <= 4 * NL;
+  const size_t plane_sz = (size_t)H * W;
+  const float* src0 = x + (size_t)ybeg * W + xb;
+  typedef float aa_f4 __attribute__((ext_vector_type(4)));
+  aa_f4 v[NL];
+#define EQA_AA_PF_LOAD(plane_)                                                                                          \
+  do {                                                                                                                  \
+    const float* src_ = src0 + (size_t)(plane_) * plane_sz;                                                             \
+    _Pragma("unroll") for (int k = 0; k < NL; ++k)                                                           \
+      v[k] = *reinterpret_cast<const aa_f4*>(src_ + (size_t)min(tr + 4 * k, nrows - 1) * W + 4 * min(tq, nq - 1));     \
+  } while (0)
+  __builtin_amdgcn_s_waitcnt(0x0070);   // the tables have arrived: from here on only row loads are outstanding (see above)
+  if (prefetch && img0 < nimg) EQA_AA_PF_LOAD((size_t)img0 * C);
+  const int nout = nband * OW;          // <= kAaNhwcTrips * kThreads (the host checks)
+  float mx = 0.0f;
+  for (int img = img0; img < nimg; img += img_step) {
+    float o[kAaNhwcTrips][C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const size_t plane = (size_t)img * C + c;
+      if (prefetch) {
+        if (tq < nq) {
+#pragma unroll
+          for (int k = 0; k < NL; ++k)
+            if (tr + 4 * k < nrows) *reinterpret_cast<aa_f4*>(rows + (tr + 4 * k) * xl + 4 * tq) = v[k];
+        }
+        if (c + 1 < C) EQA_AA_PF_LOAD(plane + 1);
+        else if (img + img_step < nimg) EQA_AA_PF_LOAD((size_t)(img + img_step) * C);
+      } else {
+        const float* src = src0 + plane * plane_sz;
+        for (int q = tq; q < nq; q += 64)
+          for (int rb = tr; rb < nrows; rb += 4) *reinterpret_cast<aa_f4*>(rows + rb * xl + 4 * q) = *reinterpret_cast<const aa_f4*>(src + (size_t)rb * W + 4 * q);
+      }
+      __syncthreads();
+      // horizontal pass: crop_resize_aa_staged_kernel's, addition for addition
+      if (rsub < rows_par) {
+        for (int ry0 = rsub; ry0 < nrows; ry0 += 4 * rows_par) {
+          float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float* row = rows + min(ry0 + u * rows_par, nrows - 1) * xl;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+              acc[u] += wv[j] * row[xo[j]];
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (ry0 + u * rows_par < nrows) tmp[(ry0 + u * rows_par) * OW + ox] = acc[u];
+        }
+      }
+      __syncthreads();
+      // vertical pass, into registers: result t of this thread is element threadIdx.x + t * kThreads of the band's (row, column)
+      // run, i.e. (r, oxx) stepped from (rsub, ox) by kThreads elements a trip (no division per value)
+      int r = rsub, oxx = ox;
+#pragma unroll
+      for (int t = 0; t < kAaNhwcTrips; ++t) {
+        float acc = 0.0f;
+        if (r < nband) {
+          const int ys = taby[r];
+#pragma unroll
+          for (int j = 0; j < K; ++j)
+            acc += tabw[r * K + j] * tmp[min(ys + j, nrows - 1) * OW + oxx];
+        }
+        o[t][c] = acc;
+        r += rows_par;
+        oxx += kThreads - rows_par * OW;
+        if (oxx >= OW) { oxx -= OW; ++r; }
+      }
+      __syncthreads();   // the next plane's passes overwrite rows and tmp
+    }
+    float* dst = y + ((size_t)img * OH + r0) * OW * C;   // the band of an image: one run of nout * C floats
+#pragma unroll
+    for (int t = 0; t < kAaNhwcTrips; ++t) {
+      const int idx = (int)threadIdx.x + t * kThreads;
+      if (idx < nout) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          dst[(size_t)idx * C + c] = o[t][c];
+          mx = fmaxf(mx, fabsf(o[t][c]));
+        }
+      }
+    }
+  }
+#undef EQA_AA_PF_LOAD
+  if (slots) {   // one per block, written whatever the block did (a block without an image: 0)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      slots[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+  }
+}
+
+// what the channels-last launch and its slot query share: the staged kernel's band and LDS rules, and a grid of image groups
+struct AaNhwcPlan {
+  int band, cap_rows, xb, xl, nbands, groups;
+  size_t lds;
+  bool few;
+};
+
+int aa_nhwc_plan(int nimg, int C, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span, AaNhwcPlan& p) {
+  if (nimg < 0 || C <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || K <= 0 || max_rows <= 0) return EQA_ERR_INVALID_ARG;
+  if ((C != 1 && C != 3) || K > EQA_AA_WIDE_MIN_K || (W & 3) != 0 || x_span <= 0 || x_begin < 0 || x_begin + x_span > W) return EQA_ERR_UNSUPPORTED;
+  p.xb = x_begin & ~3;
+  p.xl = std::min(W, (x_begin + x_span + 3) & ~3) - p.xb;
+  auto staged_lds = [&](int bnd) { return ((size_t)(bnd / kAaBand) * max_rows * (p.xl + OW) + bnd * (EQA_AA_WIDE_MIN_K + 1)) * sizeof(float); };
+  p.band = OH >= 64 ? 16 : 8;
+  if (p.band == 16 && (staged_lds(16) > 64 * 1024 || 16 * K > kThreads || 16 * OW > kAaNhwcTrips * kThreads)) p.band = 8;
+  p.cap_rows = (p.band / kAaBand) * max_rows;
+  p.lds = staged_lds(p.band);
+  if (p.lds > 64 * 1024 || p.band * K > kThreads || p.band * OW > kAaNhwcTrips * kThreads || OW > kThreads) return EQA_ERR_UNSUPPORTED;
+  // about three resident blocks per CU in all (what the band's LDS admits at the headline), each walking images: every block is
+  // resident from the start, and the consumer reads one slot per block
+  static const int per_cu = [] { const char* e = getenv("EQA_AA_NHWC_BLOCKS_PER_CU"); return e ? std::max(1, atoi(e)) : 3; }();
+  p.nbands = (OH + p.band - 1) / p.band;
+  p.groups = std::max(1, (std::min(nimg, (256 * per_cu + p.nbands - 1) / p.nbands) + kXcd - 1) / kXcd);
+  p.few = p.cap_rows <= 20;
+  return p.groups > 65535 ? EQA_ERR_UNSUPPORTED : EQA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int eqa_crop_resize_aa_nhwc_slots(int nimg, int C, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span) {
+  AaNhwcPlan p;
+  const int rc = aa_nhwc_plan(nimg, C, H, W, OH, OW, K, max_rows, x_begin, x_span, p);
+  return rc != EQA_OK ? rc : kXcd * p.nbands * p.groups;
+}
+
+int eqa_crop_resize_aa_nhwc(const float* x, float* y, const float* wx, const int32_t* x0, const float* wy, const int32_t* y0, int nimg,
+                            int C, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span, float* slots, void* stream) {
+  if (!x || !y || !wx || !x0 || !wy || !y0) return EQA_ERR_INVALID_ARG;
+  AaNhwcPlan p;
+  const int rc = aa_nhwc_plan(nimg, C, H, W, OH, OW, K, max_rows, x_begin, x_span, p);
+  if (rc != EQA_OK) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return EQA_ERR_UNSUPPORTED;
+  const dim3 grid(kXcd, p.nbands, p.groups);   // (no images: every block still writes its slot, 0)
+#define EQA_AA_NHWC_C(K_, C_)                                                                                                          \
+  do {                                                                                                                                 \
+    if (p.band == 16)                                                                                                                  \
+      hipLaunchKernelGGL((crop_resize_aa_nhwc_kernel<K_, 16, 10, C_>), grid, dim3(kThreads), p.lds, (hipStream_t)stream, x, y, wx, x0, wy, \
+                         y0, nimg, H, W, OH, OW, p.cap_rows, p.xb, p.xl, slots);                                                       \
+    else if (p.few)                                                                                                                    \
+      hipLaunchKernelGGL((crop_resize_aa_nhwc_kernel<K_, 8, 5, C_>), grid, dim3(kThreads), p.lds, (hipStream_t)stream, x, y, wx, x0, wy,  \
+                         y0, nimg, H, W, OH, OW, p.cap_rows, p.xb, p.xl, slots);                                                       \
+    else                                                                                                                               \
+      hipLaunchKernelGGL((crop_resize_aa_nhwc_kernel<K_, 8, 10, C_>), grid, dim3(kThreads), p.lds, (hipStream_t)stream, x, y, wx, x0, wy, \
+                         y0, nimg, H, W, OH, OW, p.cap_rows, p.xb, p.xl, slots);                                                       \
+  } while (0)
+#define EQA_AA_NHWC(K_)                                    \
+  case K_:                                                 \
+    if (C == 3) EQA_AA_NHWC_C(K_, 3);                      \
+    else EQA_AA_NHWC_C(K_, 1);                             \
+    break
+  switch (K) {
+    EQA_AA_NHWC(1); EQA_AA_NHWC(2); EQA_AA_NHWC(3); EQA_AA_NHWC(4); EQA_AA_NHWC(5); EQA_AA_NHWC(6); EQA_AA_NHWC(7); EQA_AA_NHWC(8);
+    default: return EQA_ERR_UNSUPPORTED;
+  }
+#undef EQA_AA_NHWC
+#undef EQA_AA_NHWC_C
+  return launch_status();
+}
 
 int eqa_crop_resize_aa(const float* x, float* y, const float* wx, const int32_t* x0, const float* wy, const int32_t* y0,
                        int planes, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span, void* stream) {

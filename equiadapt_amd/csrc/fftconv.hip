@@ -1218,12 +1218,12 @@ int eqa_fft48k5_output_stats(const float* Mo, float* T2, float* y, double* parti
   return FftK<5>::output<0>(Mo, T2, nullptr, 0, y, nimg, OH, OW, C, (hipStream_t)stream, opt);
 }
 
-int eqa_fft48k5_output_sums(const float* Mo, float* T2, const float* bias, int relu, double* S, void* workspace, int nimg,
-                            int OH, int OW, int C, int k_next, void* stream) {
-  if (!fft_map_args_ok(Mo, T2, S, nimg, OH, OW, C) || !workspace || k_next <= 0) return EQA_ERR_INVALID_ARG;
+// the inverse transform up to the window-sum partials: `workspace` (nimg, pieces, C, 2 k_next - 1), pieces = nseg_sub[0], every
+// segment in nseg_sub[1] consecutive pieces -- what window_sums_nhwc_finalize_kernel and eqa_window_sums_tail read
+static int fft48k5_output_partials(const float* Mo, float* T2, const float* bias, int relu, void* workspace, int nimg, int OH, int OW, int C,
+                                   int k_next, int* nseg_sub, void* stream) {
   const int nb = k_next - 1;
   if ((nb != 4 && nb != 2) || OH < 2 * nb + 1 || OW < 2 * nb + 1 || k_next > kMaxWinK || nimg > 65535) return EQA_ERR_UNSUPPORTED;
-  if (nimg == 0) return EQA_OK;
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)workspace;  // (nimg, OH, TX, C, 1 + 2 nb) floats
   int form = 0;
@@ -1238,7 +1238,25 @@ int eqa_fft48k5_output_sums(const float* Mo, float* T2, const float* bias, int r
   // interior pieces per tile row: 1 (one block per item), 5 (pipeline: one per consumer wave)
   const int per_row = form == 3 ? kPipeCons / 64 : form;
   const int nseg = form ? 2 * nb + per_row * fft_ntiles(OH, kFftO) : OH;
-  return eqa::launch_window_sums_nhwc_finalize(part, S, nimg, C, k_next, nseg * sub, st, sub);
+  nseg_sub[0] = nseg * sub;
+  nseg_sub[1] = sub;
+  return EQA_OK;
+}
+
+int eqa_fft48k5_output_sums(const float* Mo, float* T2, const float* bias, int relu, double* S, void* workspace, int nimg,
+                            int OH, int OW, int C, int k_next, void* stream) {
+  if (!fft_map_args_ok(Mo, T2, S, nimg, OH, OW, C) || !workspace || k_next <= 0) return EQA_ERR_INVALID_ARG;
+  int nseg_sub[2] = {0, 1};
+  if (nimg == 0) return (k_next == 3 || k_next == 5) && OH >= 2 * k_next - 1 && OW >= 2 * k_next - 1 ? EQA_OK : EQA_ERR_UNSUPPORTED;
+  const int rc = fft48k5_output_partials(Mo, T2, bias, relu, workspace, nimg, OH, OW, C, k_next, nseg_sub, stream);
+  if (rc != EQA_OK) return rc;
+  return eqa::launch_window_sums_nhwc_finalize((const float*)workspace, S, nimg, C, k_next, nseg_sub[0], (hipStream_t)stream, nseg_sub[1]);
+}
+
+int eqa_fft48k5_output_sums_partials(const float* Mo, float* T2, const float* bias, int relu, void* workspace, int nimg, int OH, int OW,
+                                     int C, int k_next, int* nseg_sub, void* stream) {
+  if (!fft_map_args_ok(Mo, T2, workspace, nimg, OH, OW, C) || !nseg_sub || k_next <= 0 || nimg == 0) return EQA_ERR_INVALID_ARG;
+  return fft48k5_output_partials(Mo, T2, bias, relu, workspace, nimg, OH, OW, C, k_next, nseg_sub, stream);
 }
 
 int eqa_fft48_supported(int ksize) { return fft_ksize_ok(ksize) ? 1 : 0; }

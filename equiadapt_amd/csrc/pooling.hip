@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kThreads) void group_pool_partial_kernel(const floa
 
 // one wave per image: lanes g < G own one orientation each; argmax by butterfly shuffles with
 // (value, index) pairs, smaller index winning ties == torch.argmax's first-maximum rule.
-__device__ __forceinline__ void wave_argmax_store(float v, int g, int G, int32_t* out) {
+__device__ __forceinline__ int wave_argmax(float v, int g, int G) {   // -> the index, in every lane
   int idx = (g < G) ? g : 0x7fffffff;
   float val = (g < G) ? v : -INFINITY;
   // NaN handling as torch: a NaN is "greater" than everything; first NaN wins.
@@ -64,6 +64,11 @@ __device__ __forceinline__ void wave_argmax_store(float v, int g, int G, int32_t
     else take = (ov > val) || (ov == val && oi < idx);
     if (take) { val = ov; idx = oi; isn = on; }
   }
+  return idx;
+}
+
+__device__ __forceinline__ void wave_argmax_store(float v, int g, int G, int32_t* out) {
+  const int idx = wave_argmax(v, g, G);
   if (g == 0) *out = idx;
 }
 
@@ -362,6 +367,86 @@ __global__ __launch_bounds__(kThreads) void window_sums_nhwc_segment_kernel(cons
 // Then one thread per channel assembles the k*k window sums from the totals and the 2(k-1) border-row segments.
 constexpr int kFinThreads = 320;   // k = 5: a block's run is 32 channels x 9 values = 288 elements -- one trip of 320 threads, not two of 256
 
+// The two steps of the finalize kernel, stated once: window_sums_tail_kernel below runs them for a whole image.
+// Step 1, one element (channel, value) of the partials: q = its first piece, the pieces of the segment axis seg_stride apart.  The
+// 2 nb border-row sums go to brd[i * brd_stride] (fp32), the total over every segment is returned (fp64, ascending segment order).
+template <int MAXB>
+__device__ __forceinline__ double ws_fin_walk(const float* __restrict__ q, size_t seg_stride, int nb, int nseg, int sub, float* brd,
+                                              int brd_stride) {
+  double acc = 0.0;
+  int s = 0;
+  if (sub <= 2) {
+    // border-row segments are needed individually as well.  All their pieces are requested before the first is used (the
+    // rolled form paid one round trip per piece, 16 in a row at k = 5: most of the kernel's 39 us for 85 MB)
+    float v[2 * MAXB][2];
+#pragma unroll
+    for (int i = 0; i < 2 * MAXB; ++i)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) v[i][t] = (i < 2 * nb && t < sub) ? q[(size_t)(i * sub + t) * seg_stride] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 2 * MAXB; ++i) {
+      if (i < 2 * nb) {
+        const float w = sub == 2 ? v[i][0] + v[i][1] : v[i][0];
+        brd[i * brd_stride] = w;
+        acc += (double)w;
+      }
+    }
+    s = 2 * nb;
+  } else {
+    for (; s < 2 * nb; ++s) {
+      float v = q[(size_t)(s * sub) * seg_stride];
+      for (int t = 1; t < sub; ++t) v += q[(size_t)(s * sub + t) * seg_stride];
+      brd[s * brd_stride] = v;
+      acc += (double)v;
+    }
+  }
+  s *= sub;
+  for (; s + 8 <= nseg; s += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = q[(size_t)(s + j) * seg_stride];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += (double)v[j];
+  }
+  if (s < nseg) {   // the last < 8 pieces: requested together as well (same order of additions)
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = s + j < nseg ? q[(size_t)(s + j) * seg_stride] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (s + j < nseg) acc += (double)v[j];
+  }
+  return acc;
+}
+
+// Step 2, window (u, v) of one channel from its 2 KW - 1 totals `tot` and border-row sums brd[row * brd_stride + value] (see the
+// inclusion-exclusion in the kernel below); with KW known the reads are independent instructions, the additions keep their order
+template <int KW>
+__device__ __forceinline__ double ws_fin_window(const double* tot, const float* brd, int brd_stride, int u, int v) {
+  constexpr int NB = KW - 1;
+  float p0[NB], pc[NB][NB];
+  double tc[NB];
+#pragma unroll
+  for (int r = 0; r < NB; ++r) p0[r] = brd[(r < u ? r : NB + r) * brd_stride];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int i = j < v ? 1 + j : 1 + NB + j;
+    tc[j] = tot[i];
+#pragma unroll
+    for (int r = 0; r < NB; ++r) pc[j][r] = brd[(r < u ? r : NB + r) * brd_stride + i];
+  }
+  double a = tot[0];
+#pragma unroll
+  for (int r = 0; r < NB; ++r) a -= (double)p0[r];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    a -= tc[j];
+#pragma unroll
+    for (int r = 0; r < NB; ++r) a += (double)pc[j][r];
+  }
+  return a;
+}
+
 // `sub` > 1: every segment arrives in `sub` pieces (one per tile column of the producer), laid out as consecutive segments;
 // the pieces of a border row are added up first (in fp32, as a single producer thread would have).
 template <int KW, int MAXB = kWsSmallBorder>   // the window size as a template argument (0: any): the assembly below then unrolls into independent LDS reads
@@ -378,53 +463,8 @@ __global__ __launch_bounds__(kFinThreads) void window_sums_nhwc_finalize_kernel(
   const int run = nch * nval;  // contiguous elements of this block in one (image, segment) row
   const float* base = part + ((size_t)b * nseg * C + c0) * nval;
   const size_t seg_stride = (size_t)C * nval;
-  for (int e = threadIdx.x; e < run; e += blockDim.x) {
-    const float* q = base + e;
-    double acc = 0.0;
-    int s = 0;
-    if (sub <= 2) {
-      // border-row segments are needed individually as well.  All their pieces are requested before the first is used (the
-      // rolled form paid one round trip per piece, 16 in a row at k = 5: most of the kernel's 39 us for 85 MB)
-      float v[2 * MAXB][2];
-#pragma unroll
-      for (int i = 0; i < 2 * MAXB; ++i)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) v[i][t] = (i < 2 * nb && t < sub) ? q[(size_t)(i * sub + t) * seg_stride] : 0.0f;
-#pragma unroll
-      for (int i = 0; i < 2 * MAXB; ++i) {
-        if (i < 2 * nb) {
-          const float w = sub == 2 ? v[i][0] + v[i][1] : v[i][0];
-          s_brd[i][e] = w;
-          acc += (double)w;
-        }
-      }
-      s = 2 * nb;
-    } else {
-      for (; s < 2 * nb; ++s) {
-        float v = q[(size_t)(s * sub) * seg_stride];
-        for (int t = 1; t < sub; ++t) v += q[(size_t)(s * sub + t) * seg_stride];
-        s_brd[s][e] = v;
-        acc += (double)v;
-      }
-    }
-    s *= sub;
-    for (; s + 8 <= nseg; s += 8) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = q[(size_t)(s + j) * seg_stride];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc += (double)v[j];
-    }
-    if (s < nseg) {   // the last < 8 pieces: requested together as well (same order of additions)
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = s + j < nseg ? q[(size_t)(s + j) * seg_stride] : 0.0f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (s + j < nseg) acc += (double)v[j];
-    }
-    s_tot[e] = acc;
-  }
+  for (int e = threadIdx.x; e < run; e += blockDim.x)
+    s_tot[e] = ws_fin_walk<MAXB>(base + e, seg_stride, nb, nseg, sub, &s_brd[0][e], kFinCh * kFinVals);
   __syncthreads();
   // One (channel, window) pair per thread and trip (one thread per channel doing its k*k windows in turn left 224 of the
   // block's 256 threads idle through ~1100 conditional fp64 adds: 110 of the kernel's 124 us).
@@ -442,28 +482,7 @@ __global__ __launch_bounds__(kFinThreads) void window_sums_nhwc_finalize_kernel(
     const int cl = it / kk, uv = it - cl * kk;
     const int u = uv / k, v = uv - u * k;
     if constexpr (KW > 0) {
-      constexpr int NB = KW - 1;
-      float p0[NB], pc[NB][NB];
-      double tc[NB];
-#pragma unroll
-      for (int r = 0; r < NB; ++r) p0[r] = s_brd[r < u ? r : NB + r][cl * nval];
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        const int i = j < v ? 1 + j : 1 + NB + j;
-        tc[j] = s_tot[cl * nval + i];
-#pragma unroll
-        for (int r = 0; r < NB; ++r) pc[j][r] = s_brd[r < u ? r : NB + r][cl * nval + i];
-      }
-      double a = s_tot[cl * nval];
-#pragma unroll
-      for (int r = 0; r < NB; ++r) a -= (double)p0[r];
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        a -= tc[j];
-#pragma unroll
-        for (int r = 0; r < NB; ++r) a += (double)pc[j][r];
-      }
-      out[((size_t)b * C + c0) * kk + it] = a;
+      out[((size_t)b * C + c0) * kk + it] = ws_fin_window<KW>(s_tot + cl * nval, &s_brd[0][cl * nval], kFinCh * kFinVals, u, v);
     } else {
       auto P = [&](int s, int i) { return (double)s_brd[s][cl * nval + i]; };
       double a = s_tot[cl * nval];
@@ -528,6 +547,86 @@ __global__ __launch_bounds__(THREADS) void sums_gemv_kernel(const double* __rest
   }
 }
 
+
+// The inference tail in ONE launch: window-sum partials -> (activations, first-maximum index, that element's table entries).  Every
+// image's tail is its own: a block takes one image through the finalize kernel's two steps (S stays in LDS: as separate launches S
+// went out to memory, 13 MB at the headline, and came back into a GEMV that waited on it), sums_gemv_kernel's partition, and
+// eqa_group_argmax's wave rule -- every addition in the order those kernels make it, so the bits are theirs.
+//   GEMV: sums_gemv_kernel gives column j to thread j % 256, which adds its columns in ascending order for every e; here slot
+//   t = tid % 256 does the same for the e = tid / 256 + 4 i it owns (the sums of different e never meet), then the same 64-lane
+//   __shfl_down tree (a wave holds 64 consecutive slots) and the same ascending sum over the four waves' partials.
+constexpr int kTailThreads = 1024;
+constexpr int kTailSlots = 256;                                   // == sums_gemv_kernel's THREADS
+constexpr int kTailEpt = kGemvMaxE / (kTailThreads / kTailSlots);   // activations per thread
+
+template <int KW>
+__global__ __launch_bounds__(kTailThreads) void window_sums_tail_kernel(const float* __restrict__ part, const double* __restrict__ Wm,
+                                                                        float* __restrict__ act, int32_t* __restrict__ gidx,
+                                                                        const float* __restrict__ rot_table, const float* __restrict__ ref_table,
+                                                                        float* __restrict__ rotation, float* __restrict__ reflection, int C,
+                                                                        int nseg, int sub, int E, double scale, double shift) {
+  constexpr int NB = KW - 1, NVAL = 1 + 2 * NB, KK = KW * KW;
+  extern __shared__ __attribute__((aligned(16))) double tail_smem[];
+  __shared__ double s_red[kTailSlots / 64][kGemvMaxE];
+  const int run = C * NVAL, K = C * KK;
+  double* S = tail_smem;                                // [C][KW][KW]: the window sums, as (B, C * k * k) rows of the GEMV
+  double* tot = S + K;                                  // [C][NVAL]
+  float* brd = reinterpret_cast<float*>(tot + run);     // [2 NB][C][NVAL]
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* base = part + (size_t)b * nseg * run;
+  for (int e = tid; e < run; e += kTailThreads) tot[e] = ws_fin_walk<NB>(base + e, (size_t)run, NB, nseg, sub, brd + e, run);
+  __syncthreads();
+  for (int it = tid; it < K; it += kTailThreads) {
+    const int cl = it / KK, uv = it - cl * KK;
+    const int u = uv / KW, v = uv - u * KW;
+    S[it] = ws_fin_window<KW>(tot + cl * NVAL, brd + cl * NVAL, run, u, v);
+  }
+  __syncthreads();
+  const int slot = tid & (kTailSlots - 1), e0 = tid / kTailSlots;
+  constexpr int COLS = 5;
+  double acc[kTailEpt];
+#pragma unroll
+  for (int i = 0; i < kTailEpt; ++i) acc[i] = 0.0;
+  for (int j = slot; j < K; j += COLS * kTailSlots) {
+    double s[COLS], w[COLS][kTailEpt];
+#pragma unroll
+    for (int u = 0; u < COLS; ++u) {
+      const bool in = j + u * kTailSlots < K;
+      s[u] = in ? S[j + u * kTailSlots] : 0.0;
+#pragma unroll
+      for (int i = 0; i < kTailEpt; ++i) w[u][i] = (in && e0 + 4 * i < E) ? Wm[(size_t)(e0 + 4 * i) * K + j + u * kTailSlots] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < COLS; ++u)
+#pragma unroll
+      for (int i = 0; i < kTailEpt; ++i)
+        if (e0 + 4 * i < E && j + u * kTailSlots < K) acc[i] += s[u] * w[u][i];
+  }
+  const int lane = tid & 63, wave = slot >> 6;
+#pragma unroll
+  for (int i = 0; i < kTailEpt; ++i) {
+    double v = acc[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) s_red[wave][e0 + 4 * i] = v;
+  }
+  __syncthreads();
+  if (tid < 64) {   // E <= 16: the image's activations sit in the first lanes of wave 0
+    float a = 0.0f;
+    if (tid < E) {
+      double v = 0.0;
+      for (int w = 0; w < kTailSlots / 64; ++w) v += s_red[w][tid];
+      a = (float)(v * scale + shift);
+      act[(size_t)b * E + tid] = a;
+    }
+    const int idx = wave_argmax(a, tid, E);
+    if (tid == 0) {
+      gidx[b] = idx;
+      rotation[b] = rot_table[idx];
+      if (ref_table) reflection[b] = ref_table[idx];
+    }
+  }
+}
 
 // ---- Optimized canonicalizer, inference tail (I8 / I10): embeddings of the G views -> (B, G) activations -------------------
 // z = relu(h * scale[d] + shift[d]) on (R, D) rows: BatchNorm1d (eval, folded) + ReLU of ConvNetwork's head
@@ -758,6 +857,28 @@ int eqa_window_sums_gemv(const double* S, const double* Wm, float* act, int B, i
   else
     hipLaunchKernelGGL((sums_gemv_kernel<kThreads, kGemvMaxE, 5>), dim3(B), dim3(kThreads), 0, (hipStream_t)stream, S, Wm, act, K, E, scale,
                        shift);
+  return launch_status();
+}
+
+int eqa_window_sums_tail(const float* part, const double* Wm, float* act, int32_t* gidx, const float* rot_table, const float* ref_table,
+                         float* rotation, float* reflection, int B, int C, int k, int nseg, int sub, int E, double scale, double shift,
+                         void* stream) {
+  if (B < 0 || C <= 0 || k <= 0 || E <= 0 || sub <= 0 || nseg <= 0) return EQA_ERR_INVALID_ARG;
+  if (!part || !Wm || !act || !gidx || !rot_table || !rotation || (ref_table && !reflection)) return EQA_ERR_INVALID_ARG;
+  if (nseg % sub != 0 || nseg / sub < 2 * (k - 1) + 1) return EQA_ERR_INVALID_ARG;   // 2 (k - 1) border rows and an interior segment, `sub` pieces each
+  static_assert(kTailEpt * (kTailThreads / kTailSlots) == kGemvMaxE && kTailThreads / kTailSlots == 4, "activation e = tid / 256 + 4 i");
+  const size_t nval = 2 * k - 1;
+  const size_t lds = (size_t)C * ((size_t)k * k * sizeof(double) + nval * sizeof(double) + 2 * (k - 1) * nval * sizeof(float));
+  if ((k != 3 && k != 5) || E > kGemvMaxE || lds > 152 * 1024 || (size_t)nseg * C * nval > 0x7fffffffULL) return EQA_ERR_UNSUPPORTED;
+  if (B == 0) return EQA_OK;
+  const void* kernel = k == 5 ? (const void*)window_sums_tail_kernel<5> : (const void*)window_sums_tail_kernel<3>;
+  if (lds > 64 * 1024 && !allow_dynamic_lds(kernel, 152 * 1024)) return EQA_ERR_UNSUPPORTED;
+  if (k == 5)
+    hipLaunchKernelGGL(window_sums_tail_kernel<5>, dim3(B), dim3(kTailThreads), lds, (hipStream_t)stream, part, Wm, act, gidx, rot_table,
+                       ref_table, rotation, reflection, C, nseg, sub, E, scale, shift);
+  else
+    hipLaunchKernelGGL(window_sums_tail_kernel<3>, dim3(B), dim3(kTailThreads), lds, (hipStream_t)stream, part, Wm, act, gidx, rot_table,
+                       ref_table, rotation, reflection, C, nseg, sub, E, scale, shift);
   return launch_status();
 }
 

@@ -99,6 +99,10 @@ class DiscreteGroupImageCanonicalization(DiscreteGroupCanonicalization):
         )
         self._consts: Dict[str, torch.Tensor] = {}
 
+    # the resized batch goes straight into a canonicalization network, whose first kernels read channels-last (the orbit kernel of
+    # OptimizedGroupEquivariantImageCanonicalization reads planes)
+    _network_reads_pixels = True
+
     # -- group bookkeeping -------------------------------------------------------------------------
 
     def _group_constants(self, device: torch.device) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -150,11 +154,31 @@ class DiscreteGroupImageCanonicalization(DiscreteGroupCanonicalization):
         raise NotImplementedError(
             "get_group_activations is not implemented for the DiscreteGroupImageCanonicalization class")
 
+    def _offers_element_tables(self) -> bool:
+        """Eval mode and the straight-through trick: the element is a lookup at the first maximum, which a network with a fused
+        tail (``element_tables`` / ``last_element``: ESCNNEquivariantNetwork) can hand over with its activations."""
+        return not self.training and self.gradient_trick == "straight_through" and hasattr(self.canonicalization_network, "element_tables")
+
+    def _element_from_network(self, group_activations: torch.Tensor) -> Optional[dict]:
+        """The element the network computed beside exactly this activations tensor, or None (it is computed here then)."""
+        offer = getattr(self.canonicalization_network, "last_element", None) if self._offers_element_tables() else None
+        if offer is None or offer[0] is not group_activations:
+            return None
+        element = {"rotation": offer[2]}
+        if offer[3] is not None:
+            element["reflection"] = offer[3]
+        element["group_index"] = offer[1]
+        return element
+
     def get_groupelement(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Image batch -> group element per image; records activations/element in the info dict (:152-172)."""
         group_activations = self.get_group_activations(x)
-        group_index = self.group_index(group_activations)
-        element = self.groupactivations_to_groupelement(group_activations, group_index)
+        element = self._element_from_network(group_activations)
+        if element is None:
+            group_index = self.group_index(group_activations)
+            element = self.groupactivations_to_groupelement(group_activations, group_index)
+        else:
+            group_index = element["group_index"]
         if not hasattr(self, "canonicalization_info_dict"):
             self.canonicalization_info_dict = {}
         # "group_index" stays out of the element dict callers iterate over (they test `"reflection" in ...`)
@@ -188,7 +212,7 @@ class DiscreteGroupImageCanonicalization(DiscreteGroupCanonicalization):
                 t = geometry.aa_resize_tables(tuple(x.shape[-2:]), crop.size, out_hw)
                 tabs = tuple(v.to(x.device) if isinstance(v, torch.Tensor) else v for v in t)
                 self._consts[key] = tabs
-            return ops.crop_resize_aa(x, tabs, out_hw)
+            return ops.crop_resize_aa(x, tabs, out_hw, pixels=getattr(self, "_network_reads_pixels", True))   # (the continuous-group canonicalizers borrow this method)
         return resize(crop(x))
 
     # -- the hot path ------------------------------------------------------------------------------
@@ -276,7 +300,14 @@ class GroupEquivariantImageCanonicalization(DiscreteGroupImageCanonicalization):
 
     def get_group_activations(self, x: torch.Tensor) -> torch.Tensor:
         x = self.transformations_before_canonicalization_network_forward(x)
-        return self.canonicalization_network(x)
+        if not (self._offers_element_tables() and x.is_cuda):
+            return self.canonicalization_network(x)
+        net = self.canonicalization_network
+        net.element_tables = self._group_constants(x.device)
+        try:
+            return net(x)
+        finally:
+            net.element_tables = None
 
 
 class OptimizedGroupEquivariantImageCanonicalization(DiscreteGroupImageCanonicalization):
@@ -285,6 +316,8 @@ class OptimizedGroupEquivariantImageCanonicalization(DiscreteGroupImageCanonical
     Reference: discrete_group.py:320-512.  The orbit (all G views of the resized batch) is written by one
     kernel launch (``eqa_orbit_expand_fwd``) instead of G x (pad, rotate, flip, crop) + ``torch.cat``.
     """
+
+    _network_reads_pixels = False
 
     def __init__(self, canonicalization_network: torch.nn.Module, canonicalization_hyperparams: Any, in_shape: tuple):
         super().__init__(canonicalization_network, canonicalization_hyperparams, in_shape)

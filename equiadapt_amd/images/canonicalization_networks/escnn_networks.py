@@ -34,6 +34,7 @@ from equiadapt_amd.images.canonicalization_networks.pooling import (
     WindowSumsLinearFn,
     conv_then_group_pool,
     group_pool,
+    sums_tail_operands,
     window_grad_table,
     window_sums_to_activations,
 )
@@ -280,6 +281,14 @@ class ESCNNEquivariantNetwork(nn.Module):
         self.eqv_network = nn.Sequential(*mods)
         self._dense: Sequence = ()
         self._cache = DerivedCache()
+        # The inference tail in one launch (eqa_window_sums_tail).  A canonicalizer that wants the element with the activations sets
+        # `element_tables` = (rotation, reflection or None) device tables around its call; where the fused tail ran, `last_element` =
+        # (the activations tensor returned, index, rotation, reflection or None), else None.  `last_routes`: what the last
+        # inference call ran -- one word per layer, "bound:<where the fused lifting kernel's pixel bound came from>" behind a
+        # fused lifting layer, "tail:<launches of the tail>" at the end.
+        self.element_tables = None
+        self.last_element = None
+        self.last_routes: List[str] = []
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         """A checkpoint of the reference's e2cnn network (escnn_networks.py:48-91) cannot be loaded by key: e2cnn stores a flat
@@ -430,9 +439,11 @@ class ESCNNEquivariantNetwork(nn.Module):
         nhwc = (self.out_channels * self.num_group_elements) % 4 == 0
         h = x.contiguous(memory_format=torch.channels_last) if nhwc else x
         pending = None  # bias of the previous layer whose (bias + ReLU) has not been applied to `h` yet
+        self.last_element, self.last_routes = None, []
         for i, (conv, bn) in enumerate(zip(convs[:-1], norms)):
             bank, bias = self._folded(conv, bn)
             route, sums, m = self._route(i, h, bank, convs, nhwc)
+            self.last_routes.append(route)
             k, (H, W) = conv.kernel_size, h.shape[-2:]
             last_before_tail, shift = i == len(convs) - 2, None
             if route != "fft5" and isinstance(h, (fftconv.GroupedMap, fftconv.LiftedInput)):
@@ -448,7 +459,15 @@ class ESCNNEquivariantNetwork(nn.Module):
                 else:
                     Bf = self._cache.derived(conv, (conv, "fft"), lambda: fftconv.spectra_for_k(bank))
                     if route == "fft5":
-                        h = fftconv.conv5x5(h, Bf, bias, True, in_bias, in_bias is not None, sums_k=sums_k)
+                        lifted = h if isinstance(h, fftconv.LiftedInput) else None
+                        operands = sums_tail_operands(tail, bank.shape[0], H - k + 1, W - k + 1, self.element_tables) if sums else None
+                        h = fftconv.conv5x5(h, Bf, bias, True, in_bias, in_bias is not None, sums_k=sums_k, tail=operands)
+                        if lifted is not None and lifted.bound_route:
+                            self.last_routes.append("bound:" + lifted.bound_route)
+                        if operands is not None:
+                            self.last_routes.append("tail:eqa_window_sums_tail")
+                            self.last_element = h
+                            return h[0]
                     else:
                         h = fftconv.conv_kxk(h, Bf, k, bias, True, in_bias, in_bias is not None)
             else:
@@ -477,8 +496,10 @@ class ESCNNEquivariantNetwork(nn.Module):
                     else:
                         h = torch.relu_(h + bias[None, :, None, None])
             if sums:
+                self.last_routes.append("tail:finalize+eqa_window_sums_gemv")
                 return window_sums_to_activations(h, tail, H - k + 1, W - k + 1)
             if last_before_tail:
+                self.last_routes.append("tail:window_sums+eqa_window_sums_gemv")
                 return conv_then_group_pool(h, tail, shift=shift, relu=shift is not None)
         raise AssertionError("unreachable: the network always has at least two convolutions")
 
@@ -593,6 +614,7 @@ class ESCNNEquivariantNetwork(nn.Module):
         return hw >= 2 * k - 1 and x.shape[-1] - (self.kernel_size - 1) * (len(convs) - 1) >= 2 * k - 1 and hw * hw <= 12288
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        self.last_element = None
         if (self.training or torch.is_grad_enabled()) and self._training_fast_path_ok(x):
             return self._forward_training(x)
         if not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32:

@@ -7,6 +7,7 @@ canonicalization network (reference: equiadapt/images/canonicalization_networks/
 GEMM library runs as a real one (see include/eqa_hip.h, eqa_fft48k5_*).  Where the tiles fit the output (88 = 2 x 44 at the
 headline shape) this needs 2.5 real multiplies per output against 4 for Winograd F(4x4,5x5), and spectra of 1.24x the
 activation size against 4x.  fp32 throughout."""
+import ctypes
 import math
 import os
 from typing import Optional
@@ -280,6 +281,7 @@ class LiftedInput:
         self.device, self.dtype, self.is_cuda = x.device, x.dtype, x.is_cuda
         self._pieces = pieces
         self._pieces_f16 = pieces_f16
+        self.bound_route: Optional[str] = None      # where `spectra_into` took the pixels' bound from, once it has run
 
     @staticmethod
     def split_f16(bank: torch.Tensor):
@@ -346,11 +348,14 @@ class LiftedInput:
         vbound = None
         if LIFT_FFT_FORM == "h2" and px % 16 == 0:      # (eqa_absmax_slots reads 16 bytes per lane)
             wh, w_scale = self.pieces_f16()
-            xbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=self.device)
-            _lib.check(lib.eqa_absmax_slots(px, self.x.numel(), xbound.data_ptr(), st), "eqa_absmax_slots")
+            xbound = ops.crop_absmax_slots(self.x)      # the resize kernel's, while nothing has written to x since
+            self.bound_route = "crop_slots" if xbound is not None else "eqa_absmax_slots"
+            if xbound is None:
+                xbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=self.device)
+                _lib.check(lib.eqa_absmax_slots(px, self.x.numel(), xbound.data_ptr(), st), "eqa_absmax_slots")
             if want_dc:
                 vbound = torch.empty(DCMAX_SLOTS, dtype=torch.float32, device=self.device)
-            _lib.check(lib.eqa_lift5_fft48k5_input_f16x2(px, wh.data_ptr(), w_scale, xbound.data_ptr(), DCMAX_SLOTS, p_b, int(self.relu), pV,
+            _lib.check(lib.eqa_lift5_fft48k5_input_f16x2(px, wh.data_ptr(), w_scale, xbound.data_ptr(), xbound.numel(), p_b, int(self.relu), pV,
                                                          vbound.data_ptr() if want_dc else None, *dims), "eqa_lift5_fft48k5_input_f16x2")
         elif LIFT_FFT_FORM == "bf16x3":                 # (this form has no variant that hands the DC bins over)
             _lib.check(lib.eqa_lift5_fft48k5_input_bf16x3(px, self.pieces().data_ptr(), p_b, int(self.relu), pV, *dims),
@@ -542,12 +547,14 @@ def spectra_for_k(bank: torch.Tensor, correlate: bool = True):
 
 
 def conv_kxk(x: torch.Tensor, B, k: int, bias: Optional[torch.Tensor], relu: bool, in_bias: Optional[torch.Tensor] = None,
-             in_relu: bool = False, keep_V: Optional[list] = None, sums_k: int = 0, stats: Optional[list] = None) -> torch.Tensor:
+             in_relu: bool = False, keep_V: Optional[list] = None, sums_k: int = 0, stats: Optional[list] = None, tail=None) -> torch.Tensor:
     """x: channels-last (nimg,Cin,H,W) -> channels-last (nimg,Cout,H-k+1,W-k+1) = [relu](conv2d(act(x), g) + bias) with
     B = spectra_for_k(g) (either form) and act(x) = [relu](x + in_bias[c]) applied while loading.
     ``keep_V``: a list that receives the input spectra V (training: the filter gradient reuses them).
     k = 5 only (`conv5x5`): x may be a `GroupedMap` or a `LiftedInput`; ``sums_k`` > 0: return instead the (nimg, Cout, sums_k, sums_k)
-    fp64 window sums of that output (the linearised last layer consumes only those); ``stats``: a list that receives the
+    fp64 window sums of that output (the linearised last layer consumes only those), or, with ``tail`` = the operands
+    `pooling.sums_tail_operands` built, what the whole tail makes of them in one launch on the inverse transform's partials:
+    (activations, index, rotation, reflection) of `ops.window_sums_tail`; ``stats``: a list that receives the
     (rows, Cout, 2) fp64 partial sums of the output's per-channel sum / sum of squares, taken by the inverse transform (training,
     no bias / activation; the caller checks ``output_stats_supported``)."""
     lib = _lib.load()
@@ -585,8 +592,14 @@ def conv_kxk(x: torch.Tensor, B, k: int, bias: Optional[torch.Tensor], relu: boo
         del V
         T2 = _workspace(k, nimg, OH, OW, Cout, dev)
         if sums_k:
-            S = torch.empty((nimg, Cout, sums_k, sums_k), dtype=torch.float64, device=dev)
             ws = torch.empty(nimg * OH * TX * Cout * (2 * sums_k - 1), dtype=torch.float32, device=dev)
+            if tail is not None:
+                nseg_sub = (ctypes.c_int * 2)()
+                with _timed("fft_output_partials"):
+                    _lib.check(lib.eqa_fft48k5_output_sums_partials(Mo.data_ptr(), T2.data_ptr(), p_bias, int(relu), ws.data_ptr(), nimg, OH, OW,
+                                                                    Cout, sums_k, nseg_sub, st), "eqa_fft48k5_output_sums_partials")
+                return ops.window_sums_tail(ws, nimg, Cout, sums_k, nseg_sub[0], nseg_sub[1], *tail)
+            S = torch.empty((nimg, Cout, sums_k, sums_k), dtype=torch.float64, device=dev)
             with _timed("fft_output_sums"):
                 _lib.check(lib.eqa_fft48k5_output_sums(Mo.data_ptr(), T2.data_ptr(), p_bias, int(relu), S.data_ptr(), ws.data_ptr(),
                                                        nimg, OH, OW, Cout, sums_k, st), "eqa_fft48k5_output_sums")
@@ -607,10 +620,11 @@ def conv_kxk(x: torch.Tensor, B, k: int, bias: Optional[torch.Tensor], relu: boo
 
 def conv5x5(x: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor], relu: bool,
             in_bias: Optional[torch.Tensor] = None, in_relu: bool = False, sums_k: int = 0,
-            keep_V: Optional[list] = None, stats: Optional[list] = None) -> torch.Tensor:
+            keep_V: Optional[list] = None, stats: Optional[list] = None, tail=None) -> torch.Tensor:
     """`conv_kxk` at k = 5, B = spectra_for(g): channels-last (nimg,Cin,H,W), a `GroupedMap` or a `LiftedInput` -> channels-last
-    (nimg,Cout,H-4,W-4), or its window sums (``sums_k``), or the map and its batch-norm statistics (``stats``)."""
-    return conv_kxk(x, B, 5, bias, relu, in_bias, in_relu, keep_V, sums_k, stats)
+    (nimg,Cout,H-4,W-4), or its window sums (``sums_k``) or what the tail makes of them (``tail``), or the map and its batch-norm
+    statistics (``stats``)."""
+    return conv_kxk(x, B, 5, bias, relu, in_bias, in_relu, keep_V, sums_k, stats, tail)
 
 
 def grad_spectra(dy: torch.Tensor, k: int = 5) -> torch.Tensor:

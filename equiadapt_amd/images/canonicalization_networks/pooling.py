@@ -58,6 +58,23 @@ def window_sums_to_activations(S: torch.Tensor, layer, H: int, W: int) -> torch.
     return act.float()
 
 
+def sums_tail_operands(layer, cin: int, H: int, W: int, tables):
+    """The operands of ``ops.window_sums_tail`` for `layer` on an (H, W) map of `cin` channels and the canonicalizer's element
+    `tables` (rotation, reflection or None; fp32, one entry per group element), or None where that launch does not apply and the
+    tail runs as `window_sums_to_activations` and the canonicalizer's own lookups (``EQA_TAIL_FUSED=0`` forces that)."""
+    if tables is None or os.environ.get("EQA_TAIL_FUSED", "1") == "0" or torch.is_grad_enabled():
+        return None
+    k, O = layer.kernel_size, layer.out_channels
+    weff, shift = layer.mean_response_weights(), layer.mean_bias_value()
+    E = weff.shape[0]
+    rot, ref = tables
+    if not (isinstance(shift, float) and weff.is_cuda and ops.window_sums_tail_supported(cin, k, E)):
+        return None
+    if any(t is not None and (t.dtype != torch.float32 or t.device != weff.device or t.numel() != E or not t.is_contiguous()) for t in (rot, ref)):
+        return None
+    return weff, 1.0 / float(O * (H - k + 1) * (W - k + 1)), shift, rot, ref
+
+
 class WindowSumsLinearFn(torch.autograd.Function):
     """act = scale * S . weff^T, the GEMV of the linearised last layer, with its backward (dS = scale * dact . weff,
     dweff = scale * dact^T . S) on the library's kernels: eqa_window_sums_gemv / eqa_window_sums_gemv_bwd.  S:(B,K) fp64,

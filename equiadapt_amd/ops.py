@@ -3,11 +3,13 @@
 Every function takes ROCm ("cuda") fp32 tensors, launches on torch's current HIP stream and returns
 torch tensors; nothing here computes on the CPU.  torch is plumbing only: device memory + streams.
 """
+import os
 from typing import Optional, Tuple
 
 import torch
 
 from equiadapt_amd import _lib
+from equiadapt_amd.common.derived import _stamp
 
 
 MAX_WINDOW_K = 10   # == kMaxWinK (csrc/eqa_common.hpp): the largest window the window-sum kernels take (the linearised last layer)
@@ -429,19 +431,43 @@ def vnsmall_canonicalize(x: torch.Tensor, params: torch.Tensor, k: int = 20, poo
     return vec, R, y
 
 
-def crop_resize_aa(x: torch.Tensor, tables, out_hw: Tuple[int, int]) -> torch.Tensor:
+def crop_resize_aa(x: torch.Tensor, tables, out_hw: Tuple[int, int], pixels: bool = True) -> torch.Tensor:
     """I1: centre crop + antialiased bilinear resize in one kernel (eqa_crop_resize_aa).  ``tables`` from
-    ``geometry.aa_resize_tables`` already moved to x.device."""
+    ``geometry.aa_resize_tables`` already moved to x.device.  ``pixels``: the consumer reads channels-last (the canonicalization
+    networks' lifting kernels): where eqa_crop_resize_aa_nhwc takes the shape the result is channels-last, same values."""
     lib = _lib.load()
     x = _need(x, "x")
     wx, x0, wy, y0, K, max_rows, x_begin, x_span = tables
     B, C, H, W = x.shape
+    OH, OW = out_hw
+    if pixels and os.environ.get("EQA_HEAD_FUSED", "1") != "0" and B > 0 and C in (1, 3) and x.data_ptr() % 16 == 0:
+        # channels-last, with the bound the fused lifting kernel scales its pixels by (eqa_crop_resize_aa_nhwc): the network's
+        # .contiguous(channels_last) returns this very tensor, and `crop_absmax_slots` hands the bound over while it is unchanged
+        nslots = lib.eqa_crop_resize_aa_nhwc_slots(B, C, H, W, OH, OW, K, max_rows, x_begin, x_span)
+        if nslots > 0:
+            y = torch.empty((B, OH, OW, C), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
+            slots = torch.empty((nslots,), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device), _timed("crop_resize_aa_nhwc"):
+                st = lib.eqa_crop_resize_aa_nhwc(x.data_ptr(), y.data_ptr(), wx.data_ptr(), x0.data_ptr(), wy.data_ptr(), y0.data_ptr(),
+                                                 B, C, H, W, OH, OW, K, max_rows, x_begin, x_span, slots.data_ptr(), _stream())
+            _lib.check(st, "eqa_crop_resize_aa_nhwc")
+            y._eqa_absmax = (slots, _stamp((y,)))
+            return y
     y = torch.empty((B, C, out_hw[0], out_hw[1]), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device), _timed("crop_resize_aa"):
         st = lib.eqa_crop_resize_aa(x.data_ptr(), y.data_ptr(), wx.data_ptr(), x0.data_ptr(), wy.data_ptr(), y0.data_ptr(),
                                     B * C, H, W, out_hw[0], out_hw[1], K, max_rows, x_begin, x_span, _stream())
     _lib.check(st, "eqa_crop_resize_aa")
     return y
+
+
+def crop_absmax_slots(y: torch.Tensor) -> Optional[torch.Tensor]:
+    """The floats whose maximum is max |y|, if `y` is a channels-last result of `crop_resize_aa` that nothing has written to since
+    (the rule of common/derived.py: the same object, at the same ``_version``, over the same ``data_ptr()``); else None."""
+    kept = getattr(y, "_eqa_absmax", None)
+    if kept is None or kept[1] != _stamp((y,)):
+        return None
+    return kept[0]
 
 
 def mask_action_nearest(masks: torch.Tensor, eidx: torch.Tensor, rtheta: torch.Tensor, flags: Optional[torch.Tensor]) -> torch.Tensor:
@@ -811,6 +837,33 @@ def window_sums_gemv(S: torch.Tensor, weff: torch.Tensor, scale: float, shift) -
     if not isinstance(shift, float):
         act += shift.to(torch.float32)
     return act
+
+
+def window_sums_tail_supported(C: int, k: int, E: int) -> bool:
+    """Does `window_sums_tail` take a C-channel map in front of a k x k tail with E group elements?  (eqa_window_sums_tail keeps an
+    image's window sums, totals and border rows in one block's LDS: 560 bytes per channel at k = 5.)"""
+    return k in (3, 5) and 1 <= E <= 16 and C * (8 * k * k + 8 * (2 * k - 1) + 8 * (k - 1) * (2 * k - 1)) <= 152 * 1024
+
+
+def window_sums_tail(part: torch.Tensor, nimg: int, C: int, k: int, nseg: int, sub: int, weff: torch.Tensor, scale: float, shift: float,
+                     rot_table: torch.Tensor, ref_table: Optional[torch.Tensor]):
+    """Window-sum partials (nimg, nseg, C, 2k - 1) fp32, every segment in `sub` pieces -> (activations (nimg, E) fp32, first-maximum
+    index (nimg,) int32, rotation (nimg,), reflection (nimg,) or None) in one launch (eqa_window_sums_tail): bit for bit what the
+    finalize kernel, `window_sums_gemv`, `group_argmax` and ``torch.index_select`` on the tables give one after the other."""
+    lib = _lib.load()
+    weff = _need(weff, "weff", torch.float64)
+    E, dev = weff.shape[0], part.device
+    act = torch.empty((nimg, E), dtype=torch.float32, device=dev)
+    gidx = torch.empty((nimg,), dtype=torch.int32, device=dev)
+    rotation = torch.empty((nimg,), dtype=torch.float32, device=dev)
+    reflection = torch.empty((nimg,), dtype=torch.float32, device=dev) if ref_table is not None else None
+    with torch.cuda.device(dev), _timed("window_sums_tail"):
+        st = lib.eqa_window_sums_tail(part.data_ptr(), weff.data_ptr(), act.data_ptr(), gidx.data_ptr(), rot_table.data_ptr(),
+                                      ref_table.data_ptr() if ref_table is not None else None, rotation.data_ptr(),
+                                      reflection.data_ptr() if reflection is not None else None, nimg, C, k, nseg, sub, E, float(scale),
+                                      float(shift), _stream())
+    _lib.check(st, "eqa_window_sums_tail")
+    return act, gidx, rotation, reflection
 
 
 def window_sums_gemv_bwd(dact: torch.Tensor, weff: torch.Tensor, S: torch.Tensor, scale: float, need_dS: bool, need_dW: bool):

@@ -139,6 +139,16 @@ int eqa_group_action_fwd_hint(const float* src, float* dst, const int32_t* gidx,
  */
 int eqa_crop_resize_aa(const float* x, float* y, const float* wx, const int32_t* x0, const float* wy, const int32_t* y0,
                        int planes, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span, void* stream);
+/* The same resize for a consumer that reads pixels: x:(nimg,C,H,W) -> y:(nimg,OH,OW,C), every value bit-equal to eqa_crop_resize_aa's
+ * (same taps, weights and order of the horizontal and vertical sums).  C in {1, 3}, K <= 8, 16-byte aligned rows (W % 4 == 0, x
+ * aligned), x_span > 0 and a band of rows no wider than the kernel keeps in registers (OW <= 96 at OH >= 64, else OW <= 192):
+ * EQA_ERR_UNSUPPORTED otherwise, and the caller takes eqa_crop_resize_aa.  slots (may be NULL): one float per block of the launch,
+ * eqa_crop_resize_aa_nhwc_slots(...) of them (that many for these arguments, or the error code), each written unconditionally: the
+ * largest |y| the block stored (0 for a block without work; a NaN is ignored, an infinity is carried, as eqa_absmax_slots does), so
+ * their maximum is max |y| -- the bound eqa_lift5_fft48k5_input_f16x2 takes as (xbound, nxbound). */
+int eqa_crop_resize_aa_nhwc_slots(int nimg, int C, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span);
+int eqa_crop_resize_aa_nhwc(const float* x, float* y, const float* wx, const int32_t* x0, const float* wy, const int32_t* y0, int nimg,
+                            int C, int H, int W, int OH, int OW, int K, int max_rows, int x_begin, int x_span, float* slots, void* stream);
 
 /*
  * I6 -- nearest-neighbour group action on uint8 masks: torchvision.transforms.functional.rotate defaults
@@ -648,6 +658,19 @@ int eqa_fft48k5_filter_grad(const float* D, float* dbank, int Cout, int Cin, voi
 int eqa_fft48k5_input_grad(const float* Cg, float* T2, float* dx, int nimg, int H, int W, int C, void* stream);
 int eqa_fft48k5_output_sums(const float* Mo, float* T2, const float* bias, int relu, double* S, void* workspace, int nimg,
                             int OH, int OW, int C, int k_next, void* stream);
+/* eqa_fft48k5_output_sums up to its partials (same workspace): workspace:(nimg, pieces, C, 2 k_next - 1) floats on return, with
+ * nseg_sub[0] = pieces and nseg_sub[1] = sub (host ints): the 2 (k_next - 1) border rows, then the interior segments, each in `sub`
+ * consecutive pieces -- the operand of eqa_window_sums_tail.  nimg > 0. */
+int eqa_fft48k5_output_sums_partials(const float* Mo, float* T2, const float* bias, int relu, void* workspace, int nimg, int OH, int OW,
+                                     int C, int k_next, int* nseg_sub, void* stream);
+/* The inference tail in one launch, one block per image: partials (as above; nseg = pieces) -> the window sums S (B, C, k, k) of
+ * eqa_fft48k5_output_sums (kept on chip, never written) -> act:(B,E) = (float)(scale * S . Wm^T + shift) as eqa_window_sums_gemv
+ * (Wm:(E, C k k) fp64, E <= 16) -> gidx:(B) as eqa_group_argmax -> rotation[b] = rot_table[gidx[b]] and, where ref_table is given,
+ * reflection[b] = ref_table[gidx[b]] (tables of E floats).  Every sum is taken in the order of the kernels named, so all outputs are
+ * bit-equal to theirs.  k in {3, 5}; the image's sums must fit the LDS (C <= 256 at k = 5): EQA_ERR_UNSUPPORTED otherwise. */
+int eqa_window_sums_tail(const float* part, const double* Wm, float* act, int32_t* gidx, const float* rot_table, const float* ref_table,
+                         float* rotation, float* reflection, int B, int C, int k, int nseg, int sub, int E, double scale, double shift,
+                         void* stream);
 
 /*
  * I2a / I2b for the kernel sizes other than 5 (round 4).  The reference's kernel_size is a free constructor argument

@@ -42,6 +42,7 @@ from equiadapt_amd.images.canonicalization_networks import (  # noqa: F401
     ESCNNWideBasic,
     ESCNNWideBottleneck,
     ESCNNWRNEquivariantNetwork,
+    ResNet18Network,
     RotationEquivariantConv,
     RotationEquivariantConvLift,
     RotoReflectionEquivariantConv,
@@ -99,6 +100,8 @@ __all__ = [
     "VNBilinear", "VNLeakyReLU", "VNLinear", "VNSoftplus", "VNStdFeature",
     # the wide-ResNet canonicalization network and its blocks (escnn_networks.py:228-511; in the reference's __all__)
     "ESCNNWRNEquivariantNetwork", "ESCNNWideBasic", "ESCNNWideBottleneck",
+    # the ResNet-18 canonicalization network (custom_nonequivariant_networks.py:83-130; in the reference's __all__)
+    "ResNet18Network",
 ]
 
 __version__ = "0.1.0"

@@ -5,7 +5,7 @@ from equiadapt_amd.images.canonicalization_networks.custom_group_equivariant_lay
     RotoReflectionEquivariantConv,
     RotoReflectionEquivariantConvLift,
 )
-from equiadapt_amd.images.canonicalization_networks.custom_nonequivariant_networks import ConvNetwork  # noqa: F401
+from equiadapt_amd.images.canonicalization_networks.custom_nonequivariant_networks import ConvNetwork, ResNet18Network  # noqa: F401
 from equiadapt_amd.images.canonicalization_networks.escnn_networks import (  # noqa: F401
     ESCNNEquivariantNetwork,
     ESCNNSteerableNetwork,

@@ -1,12 +1,13 @@
-"""ConvNetwork: the plain strided encoder the optimized canonicalizer scores group views with.
+"""ConvNetwork: the plain strided encoder the optimized canonicalizer scores group views with; ResNet18Network: the ResNet-18 one.
 
-Reference: equiadapt/images/canonicalization_networks/custom_nonequivariant_networks.py:8-80.
+Reference: equiadapt/images/canonicalization_networks/custom_nonequivariant_networks.py:8-130.
 Small MIOpen convolutions (PyTorch-ROCm); module / parameter names match the reference's state_dict.
-The pretrained torchvision wrappers (ResNet18Network, WideResNet*) are out of scope.
+ResNet18Network's eval forward runs 19 of its 20 convolutions on eqa_conv3x3_nhwc (csrc/conv3x3.hip).
+The wide torchvision wrappers (WideResNet50Network, WideResNet101Network) are out of scope.
 """
 import os
 import threading
-from typing import List
+from typing import List, Optional
 
 import torch
 from torch import nn
@@ -296,3 +297,191 @@ class ConvNetwork(nn.Module):
                     h = m(h)
             return self.final_fc(h.reshape(x.shape[0], -1))
         return self.final_fc(self.enc_network(x).reshape(x.shape[0], -1))
+
+
+class _BasicBlock(nn.Module):
+    """The basic residual block of the published ResNet-18 (He et al. 2015, table 1, with the stride on the first 3 x 3 layer and a
+    1 x 1 projection shortcut where the shape changes): relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut(x))."""
+
+    def __init__(self, cin: int, cout: int, stride: int):
+        super().__init__()
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.downsample: Optional[nn.Sequential] = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        return self.relu(out + (x if self.downsample is None else self.downsample(x)))
+
+
+class _ResNet18(nn.Module):
+    """ResNet-18 restated from its published definition, with the module names of torchvision's `resnet18` (so its state dict loads
+    by key) and the reference's replacement head `fc = Sequential(Linear(512, out_vector_size))`."""
+
+    def __init__(self, out_vector_size: int):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        widths = (64, 128, 256, 512)
+        for i, wd in enumerate(widths):
+            cin = widths[max(i - 1, 0)]
+            setattr(self, f"layer{i + 1}", nn.Sequential(_BasicBlock(cin, wd, 1 if i == 0 else 2), _BasicBlock(wd, wd, 1)))
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Sequential(nn.Linear(512, out_vector_size))
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1.0)
+                nn.init.constant_(m.bias, 0.0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+
+class ResNet18Network(nn.Module):
+    """ResNet-18 with a `Linear(512, out_vector_size)` head as the canonicalization network (reference:
+    custom_nonequivariant_networks.py:83-130; `network_type: non_equivariant_resnet18`).  As there, only `out_vector_size` of the
+    constructor's arguments is used.  `self.resnet18` is a plain torch module with torchvision's parameter names, so a reference
+    checkpoint loads by key.
+
+    Weights: the reference downloads torchvision's ImageNet weights in its constructor; this package downloads nothing.  The network
+    STARTS FROM RANDOM WEIGHTS (the published initialisation) unless a state dict is loaded -- a reference checkpoint through
+    `load_state_dict`, or a torchvision `resnet18` state dict through `load_torchvision_state_dict`.
+
+    Routes (`last_routes`: one string per convolution in module order, 20 entries):
+      plain   `self.resnet18(x)`: any device, dtype, training mode, autograd.  `EQA_RESNET_KERNEL=0` (read per forward) forces it, and
+              everything the fused rule does not take -- training in particular -- runs here.
+      fused   the module and all its batch-norms in eval, gradients disabled, a 4-D fp32 input with 3 channels and B >= 1 on the device,
+              parameters fp32, contiguous and on that device, no forward hooks on the submodules.  Every batch-norm is folded into the
+              convolution in front of it; the stem is the library's convolution on a channels-last input ("lib") + relu_ + max_pool2d,
+              used as a (B, h, w, 64) map without a copy; behind it every convolution is ONE launch of eqa_conv3x3_nhwc with bias
+              (the folded norm), residual add and ReLU in its epilogue: a block's conv1 "conv3x3", its projection shortcut
+              "conv1x1s2", its conv2 "conv3x3+res".  A layer `ops.conv3x3_supported` refuses, or one the gate `_kernel_pays` hands to
+              the library (wide 3 x 3 layers at 2048 output pixels and more, where the library was measured faster), runs F.conv2d on
+              the same channels-last memory + add_ + relu_ ("lib").  The tail is the mean over the pixels and F.linear.  No host
+              synchronisation: the step can be captured into a hipGraph.
+    """
+
+    def __init__(self, in_shape: tuple, out_channels: int, kernel_size: int, num_layers: int = 2, out_vector_size: int = 128):
+        super().__init__()
+        self.resnet18 = _ResNet18(out_vector_size)
+        self.out_vector_size = out_vector_size
+        self.last_routes: List[str] = []
+        self._cache = DerivedCache()
+
+    def load_torchvision_state_dict(self, state_dict) -> None:
+        """Load the backbone from a torchvision `resnet18` state dict (keys without prefix), strictly; the dict's `fc.*` (1000 ImageNet
+        classes, or any other width) is ignored and this network's head is left as it is."""
+        sd = {k: v for k, v in state_dict.items() if not k.startswith("fc.")}
+        sd.update({"fc." + k: v for k, v in self.resnet18.fc.state_dict().items()})
+        self.resnet18.load_state_dict(sd, strict=True)
+
+    def _blocks(self):
+        net = self.resnet18
+        return [b for layer in (net.layer1, net.layer2, net.layer3, net.layer4) for b in layer]
+
+    def _pairs(self):
+        """(convolution, batch-norm) in module order: the stem, then per block conv1, conv2 and the shortcut where there is one."""
+        net = self.resnet18
+        pairs = [(net.conv1, net.bn1)]
+        for b in self._blocks():
+            pairs += [(b.conv1, b.bn1), (b.conv2, b.bn2)]
+            if b.downsample is not None:
+                pairs.append((b.downsample[0], b.downsample[1]))
+        return pairs
+
+    def _fused_applies(self, x: torch.Tensor) -> bool:
+        if self.training or torch.is_grad_enabled() or os.environ.get("EQA_RESNET_KERNEL", "1") == "0":
+            return False
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and x.shape[0] >= 1):
+            return False
+        lin = self.resnet18.fc[0]
+        for m in [m for pair in self._pairs() for m in pair] + [lin]:
+            if isinstance(m, nn.BatchNorm2d) and (m.training or m.running_mean is None or not m.affine):
+                return False
+            for t in list(m._parameters.values()) + list(m._buffers.values()):
+                if t is None or t.dtype == torch.int64:          # (an absent bias; num_batches_tracked)
+                    continue
+                if t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous():
+                    return False
+        return not any(m._forward_hooks or m._forward_pre_hooks for m in self.resnet18.modules())
+
+    def _folded(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, pack: bool):
+        """(filters, bias) of ``bn(conv(.))`` in eval mode -- the filters channels-last, as the library's convolution wants them beside a
+        channels-last map -- and with `pack` the filters in eqa_conv3x3_nhwc's operand order: rebuilt when any tensor that enters them
+        has changed (common/derived.py)."""
+        def build():
+            scale, shift = bn_eval_affine(bn)
+            return (conv.weight * scale[:, None, None, None]).contiguous(memory_format=torch.channels_last), shift.contiguous()
+
+        w, b = self._cache.get(conv, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
+        if not pack:
+            return w, b
+        from equiadapt_amd import ops
+
+        return self._cache.derived(conv, (conv, "conv3x3"), lambda: ops.pack_conv3x3_weights(w)), b
+
+    @staticmethod
+    def _kernel_pays(pixels: int, cin: int, taps: int, stride: int) -> bool:
+        """The gate on shapes alone (measured: DESIGN.md section 1, "ResNet18Network"): at 2048 output pixels and more, the library's
+        convolution + add_ + relu_ is faster than the kernel on the 3 x 3 layers of 256 input channels and more, and on the stride-1
+        ones of 128 and more.  Below 2048 pixels nothing was measured slower, and everything else stays on the kernel."""
+        return not (taps == 9 and pixels >= 2048 and (cin >= 256 or (stride == 1 and cin >= 128)))
+
+    def _layer(self, h: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, res: Optional[torch.Tensor], relu: bool, routes: list, slot: int):
+        """One convolution + folded norm (+ residual) (+ ReLU) on the (B, h, w, C) map `h`: one launch where the kernel takes the shape
+        and pays; else the library's convolution on the same memory (a channels-last view) with add_ and relu_ ("lib")."""
+        from equiadapt_amd import ops
+
+        taps, stride, pad = conv.kernel_size[0] ** 2, conv.stride[0], conv.padding[0]
+        pixels = h.shape[0] * ((h.shape[1] + 2 * pad - conv.kernel_size[0]) // stride + 1) * ((h.shape[2] + 2 * pad - conv.kernel_size[0]) // stride + 1)
+        if (ops.conv3x3_supported(h.shape[0], h.shape[1], h.shape[2], conv.in_channels, conv.out_channels, taps, stride)
+                and self._kernel_pays(pixels, conv.in_channels, taps, stride)):
+            wpk, b = self._folded(conv, bn, True)
+            routes[slot] = "conv1x1s2" if taps == 1 else ("conv3x3" if res is None else "conv3x3+res")
+            return ops.conv3x3_nhwc(h, wpk, b, res, relu, taps, stride)
+        w, b = self._folded(conv, bn, False)
+        routes[slot] = "lib"
+        z = torch.nn.functional.conv2d(h.permute(0, 3, 1, 2), w, b, conv.stride, conv.padding)
+        if res is not None:
+            z.add_(res.permute(0, 3, 1, 2))
+        if relu:
+            z.relu_()
+        z = z.permute(0, 2, 3, 1)
+        return z if z.is_contiguous() else z.contiguous()
+
+    def _forward_fused(self, x: torch.Tensor) -> torch.Tensor:
+        net = self.resnet18
+        routes = ["lib"] + [""] * 19
+        w, b = self._folded(net.conv1, net.bn1, False)
+        h = torch.nn.functional.conv2d(x.contiguous(memory_format=torch.channels_last), w, b, net.conv1.stride, net.conv1.padding)
+        h = torch.nn.functional.max_pool2d(h.relu_(), 3, 2, 1).permute(0, 2, 3, 1)
+        if not h.is_contiguous():
+            h = h.contiguous()
+        slot = 1
+        for blk in self._blocks():
+            t = self._layer(h, blk.conv1, blk.bn1, None, True, routes, slot)
+            if blk.downsample is not None:
+                h = self._layer(h, blk.downsample[0], blk.downsample[1], None, False, routes, slot + 2)
+            h = self._layer(t, blk.conv2, blk.bn2, h, True, routes, slot + 1)
+            slot += 2 if blk.downsample is None else 3
+        self.last_routes = routes
+        lin = net.fc[0]
+        return torch.nn.functional.linear(h.mean(dim=(1, 2)), lin.weight, lin.bias)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._fused_applies(x):
+            return self._forward_fused(x)
+        self.last_routes = ["plain"] * 20
+        return self.resnet18(x)

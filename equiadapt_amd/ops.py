@@ -1682,3 +1682,57 @@ def gconv1x1_wgrad(x: torch.Tensor, dz: torch.Tensor) -> Tuple[torch.Tensor, tor
                                     P, Cin, Cout, _stream())
     _lib.check(st, "eqa_gconv1x1_wgrad")
     return dW, dbias
+
+
+def conv3x3_supported(n: int, h: int, w: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+    """Shapes and sizes eqa_conv3x3_nhwc takes: channel counts on the multiples of 32 from 32 to 512; taps 9 (3 x 3, padding 1) at
+    stride 1 or 2, taps 1 (1 x 1, no padding) at stride 2; x, y and res each inside one 32-bit buffer range (the size is part of the
+    query: a caller that asks first takes its other route instead of failing in the launch)."""
+    return bool(_lib.load().eqa_conv3x3_supported(n, h, w, cin, cout, taps, stride))
+
+
+def pack_conv3x3_weights(w: torch.Tensor) -> torch.Tensor:
+    """(Cout, Cin, k, k) filters, k in {1, 3}, Cin and Cout multiples of 32 -> the MFMA operand-fragment order of eqa_conv3x3_nhwc,
+    tap-major, shape (k k, Cin/16, Cout/32, 2, 64, 4):
+        Wpk[k dy + dx][s][n][b][32 h + i][t] = w[32 n + i][16 s + 8 b + 4 h + t][dy][dx]
+    (`pack_plane_gemm_weights` with the taps as planes).  A pure torch op: it works on any device."""
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.shape[2] not in (1, 3) or w.shape[0] % 32 or w.shape[1] % 32 or not w.numel():
+        raise ValueError(f"pack_conv3x3_weights takes (Cout, Cin, k, k) filters, k in (1, 3), channels on multiples of 32, got {tuple(w.shape)}")
+    Cout, Cin, k = w.shape[0], w.shape[1], w.shape[2]
+    return pack_plane_gemm_weights(w.permute(2, 3, 1, 0).reshape(k * k, Cin, Cout)).reshape(k * k, Cin // 16, Cout // 32, 2, 64, 4)
+
+
+def conv3x3_nhwc(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, res: Optional[torch.Tensor] = None, relu: bool = False,
+                 taps: int = 9, stride: int = 1) -> torch.Tensor:
+    """y = [relu](conv(x) + bias [+ res]) in one launch (eqa_conv3x3_nhwc): taps = 9 a 3 x 3 convolution with zero padding 1, taps = 1
+    a 1 x 1 one without (stride 2 only).  x: a contiguous (N, H, W, Cin) fp32 map on the device; res and the result (N, OH, OW, Cout)
+    with OH = (H + 2 pad - k) // stride + 1; wpk = pack_conv3x3_weights(filters).  No autograd."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise RuntimeError("conv3x3_nhwc expects an fp32 tensor on the device")
+    wpk = _need(wpk, "wpk")
+    if wpk.dim() != 6 or wpk.shape[0] != taps or tuple(wpk.shape[3:]) != (2, 64, 4):
+        raise ValueError(f"conv3x3_nhwc: wpk must be pack_conv3x3_weights' ({taps}, Cin/16, Cout/32, 2, 64, 4) operand, got {tuple(wpk.shape)}")
+    Cin, Cout = wpk.shape[1] * 16, wpk.shape[2] * 32
+    if x.dim() != 4 or x.shape[3] != Cin or not x.is_contiguous():
+        raise RuntimeError(f"conv3x3_nhwc: x must be a contiguous (N, H, W, {Cin}) map, got {tuple(x.shape)}")
+    N, H, W = x.shape[:3]
+    bias = _need(bias, "bias")
+    if bias.numel() != Cout:
+        raise ValueError(f"conv3x3_nhwc: bias has {Cout} entries")
+    if not conv3x3_supported(N, H, W, Cin, Cout, taps, stride):
+        raise _lib.EqaLibraryError(f"eqa_conv3x3_nhwc does not take {N} x {H} x {W} maps of {Cin} -> {Cout} channels with taps {taps}, "
+                                   f"stride {stride} (ask conv3x3_supported first)")
+    k, pad = (3, 1) if taps == 9 else (1, 0)
+    out_shape = (N, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1, Cout)
+    p_res = None
+    if res is not None:
+        if res.dtype != torch.float32 or res.device != x.device or tuple(res.shape) != out_shape or not res.is_contiguous():
+            raise RuntimeError(f"conv3x3_nhwc: res must be a contiguous fp32 {out_shape} map on x's device")
+        p_res = res.data_ptr()
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("conv3x3"):
+        st = lib.eqa_conv3x3_nhwc(x.data_ptr(), wpk.data_ptr(), bias.data_ptr(), p_res, int(relu), y.data_ptr(), N, H, W, Cin, Cout, taps,
+                                  stride, _stream())
+    _lib.check(st, "eqa_conv3x3_nhwc")
+    return y

@@ -1025,6 +1025,27 @@ int64_t eqa_steer_lift_wgrad_workspace_bytes(int Cin, int K, int fields);
 int eqa_steer_lift_wgrad(const float* x, const float* dy, void* workspace, float* dbank, int nimg, int H, int W, int Cin, int K,
                          int fields, void* stream);
 
+/*
+ * The 3 x 3 convolutions and the 1 x 1 stride-2 shortcuts of ResNet18Network's basic blocks (csrc/conv3x3.hip; reference network:
+ * custom_nonequivariant_networks.py:83-130) on a channels-last fp32 map, the block's glue in the epilogue -- one launch, one pass:
+ *   z[n][oy][ox][o] = sum_{dy,dx,c} x[n][s oy + dy - pad][s ox + dx - pad][c] W[o][c][dy][dx] + bias[o] (+ res[n][oy][ox][o])
+ *   y = relu ? max(z, 0) : z
+ * taps = 9: 3 x 3 with zero padding 1; taps = 1: 1 x 1 without padding.  stride s in {1, 2}.  x:(N,H,W,Cin); res, y:(N,OH,OW,Cout)
+ * with OH = (H + 2 pad - k) / s + 1 and OW likewise; bias:(Cout); res NULL: no residual.  y aliases neither x nor res.
+ * Wpk: W:(Cout,Cin,k,k) re-ordered tap-major into MFMA operand fragments (ops.pack_conv3x3_weights),
+ *   Wpk[3 dy + dx][s][n][b][32 h + i][t] = W[32 n + i][16 s + 8 b + 4 h + t][dy][dx]     (taps, Cin/16, Cout/32, 2, 64, 4)
+ * eqa_conv3x3_supported: Cin, Cout multiples of 32 in [32, 512] (what eqa_gconv1x1_supported admits); taps in {1, 9}, stride in
+ * {1, 2}, taps = 1 with stride 2 only; H, W >= 1 (so OH, OW >= 1); x, y and res each within one 32-bit buffer range
+ * (N H W Cin 4 and N OH OW Cout 4 bytes <= 0xffffff00) -- the size test is part of the query, so a caller that asks first never meets
+ * EQA_ERR_UNSUPPORTED from the launch for a size.  A refused shape: EQA_ERR_UNSUPPORTED before any pointer is read.  NULL x, Wpk,
+ * bias or y, or y equal to x or res: EQA_ERR_INVALID_ARG.  Pointers 16-byte aligned (else EQA_ERR_UNSUPPORTED).  Rows past the last
+ * output pixel are never written.  N = 0: nothing is launched.  fmaf chains over (tap, c) in a fixed order, no atomics: two launches
+ * on the same operands give the same bits.  Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_conv3x3_supported(long long N, int H, int W, int Cin, int Cout, int taps, int stride);
+int eqa_conv3x3_nhwc(const float* x, const float* Wpk, const float* bias, const float* res, int relu, float* y, long long N, int H, int W,
+                     int Cin, int Cout, int taps, int stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

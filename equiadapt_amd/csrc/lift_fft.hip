@@ -53,17 +53,19 @@ __device__ __forceinline__ float lf_pixel_or_zero(float v, bool ok) { return ok 
 
 #ifdef EQA_LF_CLOCK
 // Debug build: shader cycles per phase, summed over the items of block 0, by thread 0 of six waves (slot k: waves 8, 1, 0, 6, 11, 2;
-// [8 k .. 8 k + 7] for k < 5, [64 .. 71] for k = 5; [72 + k]: the slot's row passes inside the sub-phases, FORM 2's column waves),
+// [8 k .. 8 k + 7] for k < 5, [64 .. 71] for k = 5; [72 + k]: the slot's row passes inside the sub-phases, FORM 2's column waves;
+// [80 + 2 k], [81 + 2 k]: FORM 2's role work and second barrier of SUB-PHASE 0, which [8 k + 2] and [8 k + 3] then leave out),
 // HW_REG_HW_ID of every wave w of block 0 ([40 + w]; bits 5:4: its SIMD), 1 + EQA_LF_H2_ROWDEAL ([62]) and 1 + EQA_LF_H2_DEAL ([63]:
 // whether wave 6 convolves) of the h2 kernel -- tools/kbench_lift_fft.py.
 __device__ unsigned long long g_lf_clock[128];
 __device__ __forceinline__ int lf_clock_slot(int wave) { return wave == 8 ? 0 : wave == 1 ? 1 : wave == 0 ? 2 : wave == 6 ? 3 : wave == 11 ? 4 : wave == 2 ? 5 : -1; }
 #define LF_CLOCK_BEGIN() const bool lfc_on = blockIdx.x == 0 && (threadIdx.x & 63) == 0 && lf_clock_slot(wave) >= 0; \
   if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) { unsigned hw_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_)); g_lf_clock[40 + wave] = hw_; } \
-  unsigned long long lfc_t = __builtin_readcyclecounter(); unsigned lfc_s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}   /* (32 bits: a launch is < 2^32 cycles) */
+  unsigned long long lfc_t = __builtin_readcyclecounter(); unsigned lfc_s[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}   /* (32 bits: a launch is < 2^32 cycles) */
 #define LF_CLOCK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); lfc_s[i] += (unsigned)(n_ - lfc_t); lfc_t = n_; } while (0)
 #define LF_CLOCK_END() do { if (lfc_on) { const int k_ = lf_clock_slot(wave); \
-  for (int i_ = 0; i_ < 8; ++i_) g_lf_clock[(k_ < 5 ? 8 * k_ : 64) + i_] = lfc_s[i_]; g_lf_clock[72 + k_] = lfc_s[8]; } } while (0)
+  for (int i_ = 0; i_ < 8; ++i_) g_lf_clock[(k_ < 5 ? 8 * k_ : 64) + i_] = lfc_s[i_]; g_lf_clock[72 + k_] = lfc_s[8]; \
+  g_lf_clock[80 + 2 * k_] = lfc_s[9]; g_lf_clock[81 + 2 * k_] = lfc_s[10]; } } while (0)
 #else
 #define LF_CLOCK_BEGIN() do { } while (0)
 #define LF_CLOCK(i) do { } while (0)
@@ -153,6 +155,10 @@ enum { kConv = 0, kCols = 1, kRowp = 2 };   // kRowp (FORM 2, EQA_LF_H2_DEAL = 0
 //   EQA_LF_H2_DEAL = 0  FOUR convolution waves 8..11, one per SIMD, nine tiles each in column-major order (tile n: column n / 12, row
 //                       n % 12): wave 8 column 0 rows 0..8, wave 11 column 2 rows 3..11; waves 9 and 10 three rows at the end / start of a
 //                       column, then six of the middle column.  Waves 6, 7: kRowp (profiles/r07 .. r13).
+// Every sub-phase is dealt alike.  A dealing of its own for sub-phase 0, where the lone waves' SIMDs carry two column transforms each
+// (lone waves 2 or 0 tiles of tile column 0, the pairs the rest of it behind their own six: runs of 6 + 2 or 6 + 3 that cross), was
+// built, measured slower and removed: with the packed columns separated at store time (EQA_LF_H2_PACKED) the convolution sets
+// sub-phase 0, and 8 or 9 tiles take a paired wave 7 k cycles where 6 take every wave 4.8 k (profiles/r25).
 #ifndef EQA_LF_H2_DEAL
 #define EQA_LF_H2_DEAL 1
 #endif
@@ -262,6 +268,20 @@ __device__ __forceinline__ int lf_h2_rows(int wave, int s) {
 constexpr bool lf_h2_window_has_pass(int) { return false; }
 constexpr bool lf_h2_conv_rows_in_tail() { return false; }
 #endif
+
+// FORM 2's packed columns (wave 0: kx = 0 in the real part, kx = 24 in the imaginary part of one transform).  C0[ky] and C24[ky] are
+// functions of Z[ky] and Z[48 - ky]; the groups leave in ascending order, three per sub-phase, so the partners of groups 0..6 (ky >=
+// 24: groups 6..11) are still in registers when those leave.
+//   EQA_LF_H2_PACKED = 1  separated when group g leaves: the C24 line of group g goes out beside the group's own, 3 + 3 + 1 over
+//                         sub-phases 0, 1, 2, each with its share of the arithmetic.  Wave 0's sub-phase 0: 7.7 k -> 6.0 k cycles,
+//                         and the convolution waves, not wave 0, arrive last at that sub-phase's second barrier (profiles/r25)
+//   EQA_LF_H2_PACKED = 0  all of it behind the transform in sub-phase 0, the seven C24 lines at once (profiles/r07 .. r24): every
+//                         wave of the block waited for wave 0 there, 2.7 k cycles behind the slowest other column wave
+#ifndef EQA_LF_H2_PACKED
+#define EQA_LF_H2_PACKED 1
+#endif
+constexpr int kLhPacked = EQA_LF_H2_PACKED;
+static_assert(kLhPacked == 0 || kLhPacked == 1, "EQA_LF_H2_PACKED: 0 or 1");
 
 template <class F, int... Is>
 __device__ __forceinline__ void lf_for_const(F&& f, std::integer_sequence<int, Is...>) {
@@ -818,6 +838,7 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
   };
   // The pending item's share of sub-phase SUB: the transform in sub-phase 0, four of its twelve frequency groups in each.
   // Frequency of (kx, ky): interior kx: 23 ky + kx - 1; packed: 1104 + 2 ky (kx = 0), 1105 + 2 ky (kx = 24), ky <= 24 only.
+  constexpr bool kAtStore = H2 && kLhPacked == 1;    // (FORM 2 alone: the other forms keep their code)
   auto col_work = [&](auto SUB) {
     constexpr int sub = decltype(SUB)::value;
     if (!pending) return;
@@ -834,7 +855,13 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
         cre[ky] = ore[ky];
         cim[ky] = oim[ky];
       }
-      if (has_packed) {
+      if constexpr (kAtStore) {
+        // the whole spectrum exists HERE: with no reader of all of it in this block the compiler sinks the transform's last
+        // butterflies down to each group's store and keeps their inputs alive instead (188 bytes of scratch)
+#pragma unroll
+        for (int ky = 0; ky < kFftN; ++ky) asm volatile("" : "+v"(cre[ky]), "+v"(cim[ky]));
+      }
+      if (has_packed && !kAtStore) {
         // Wave 0.  The packed lanes separate their two real columns: C0 = (Z[k] + conj Z[-k]) / 2 replaces Z[k] in place (k = 0..24);
         // C24 = (Z[k] - conj Z[-k]) / 2i leaves at once (seven line stores: even lanes the real quad, odd lanes the imaginary quad,
         // received) -- kept until its turn in a later sub-phase it would cost every column wave 56 registers.
@@ -868,6 +895,30 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
 #pragma unroll
     for (int g = NGRP * sub; g < NGRP * sub + NGRP; ++g) {
       const bool live1 = !pair_packed || 4 * g + col_ci < kFftH;
+      if constexpr (kAtStore) {
+        if (has_packed && g < 7) {
+          // Wave 0, separation at store time: the same C0 and C24 (above), formed when group g leaves.  The partners Z[48 - ky] of
+          // groups 0..6 lie in groups 6..11, which leave later (group 6 needs ky = 24 alone, its own partner), so they are still in
+          // cre / cim; C0 replaces Z[ky] in the group's registers, C24 lives in eight registers for the length of its store.
+          float p24re[4], p24im[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int ky = 4 * g + i, kn = (kFftN - ky) % kFftN;
+            if (ky < kFftH) {
+              const float a = cre[ky], b = cim[ky], c2 = cre[kn], d = cim[kn];
+              p24re[i] = 0.5f * (b + d);
+              p24im[i] = 0.5f * (c2 - a);
+              cre[ky] = packed ? 0.5f * (a + c2) : a;
+              cim[ky] = packed ? 0.5f * (b - d) : b;
+            } else {
+              p24re[i] = p24im[i] = 0.0f;
+            }
+          }
+          if (g == 0) dc_seen = fmaxf(dc_seen, packed ? cre[0] : 0.0f);     // the DC bin (kx = 0, ky = 0) of this lane's channel
+          // the C24 line is the frequency behind the C0 line (1105 + 2 ky): one row further than store 1 below
+          store_pair(p24re, p24im, pair_packed && live1 ? vb1 + (unsigned)g * vs1 + (unsigned)rowb : 0xfffffff0u, 0xfffffff0u, false);
+        }
+      }
       store_pair(&cre[4 * g], &cim[4 * g], live1 ? vb1 + (unsigned)g * vs1 : 0xfffffff0u, vb2 + (unsigned)g * vs2, true);
     }
 #endif
@@ -956,9 +1007,9 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
             if (sub > 0 && (wave == 8 || wave == 9)) row_pass(8 * (sub - 1) + 4 * (wave - 8));
           }
         }
-        LF_CLOCK(2);
+        if (H2 && sub == 0) LF_CLOCK(9); else LF_CLOCK(2);
         __syncthreads();
-        LF_CLOCK(3);
+        if (H2 && sub == 0) LF_CLOCK(10); else LF_CLOCK(3);
         if constexpr (H2) {
           if (sub < NSUB - 1) stage_h(kLhSubRows * sub + kLhRing, kLhSubRows);
           else stage_h(0, kLhRing);
@@ -988,7 +1039,7 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
         }
         LF_CLOCK(1);
         col_work(SUB);
-        LF_CLOCK(2);
+        if (H2 && sub == 0) LF_CLOCK(9); else LF_CLOCK(2);
         if constexpr (H2) {
           // the wave's row pass of this window (lf_h2_rowmask: rows of an EARLIER sub-phase of the item being convolved), behind
           // the window's stores in program order: they drain while it computes.  Of the pending item's spectrum 96 - 24 (sub + 1)
@@ -1000,7 +1051,7 @@ __device__ __forceinline__ void lift5_fft48_body(const float* __restrict__ x, co
           }
         }
         __syncthreads();
-        LF_CLOCK(3);
+        if (H2 && sub == 0) LF_CLOCK(10); else LF_CLOCK(3);
         if constexpr (PIECES) {
           if (sub < NSUB - 1) {
             stage_grp(sub + 2, 0);

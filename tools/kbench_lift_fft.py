@@ -96,11 +96,15 @@ def main():
             print(f"EQA_LF_H2_DEAL = {out[63] - 1}, EQA_LF_H2_ROWDEAL = {out[62] - 1}")
         for k, (base, w, who) in enumerate(((0, 8, "convolution wave 8"), (8, 1, "column wave 1"), (16, 0, "column wave 0 (packed)"),
                                             (24, 6, wave6), (32, 11, "convolution wave 11"), (64, 2, "column wave 2"))):
-            tot = sum(out[base:base + 8]) + out[72 + k]
+            # [80 + 2 k], [81 + 2 k]: role work and barrier 2 of sub-phase 0 alone (h2; older builds: 0, there [base + 2], [base + 3] hold all four)
+            sub0 = out[80 + 2 * k] + out[81 + 2 * k]
+            tot = sum(out[base:base + 8]) + out[72 + k] + sub0
             if tot == 0:
                 continue
             at = f" [SIMD {simd[w]}]" if simd else ""
             rows = f" | row passes in the sub-phases: {out[72 + k] // items}" if form == "h2" and w < 6 and out[62] else ""
+            if form == "h2" and sub0:
+                rows += f" | sub-phase 0 (not in the two figures above): role work {out[80 + 2 * k] // items}, barrier 2 {out[81 + 2 * k] // items}"
             print(f"{who}{at}: cycles per item (block 0, {items} items): " + " | ".join(f"{n}: {out[base + i] // items}" for i, n in enumerate(names))
                   + rows + f" | total {tot // items}")
         if simd:

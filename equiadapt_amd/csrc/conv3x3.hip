@@ -17,6 +17,8 @@
 // belongs to the adjacent image, and the padding test (on iy, ix of the lane's own image) is what keeps it out.
 // Work: wave-tile = (64 output pixels, 32 NT output channels), column tiles fastest, so the waves of a block share their rows of x.
 // Rows past P are never stored (they lie outside the tile's y descriptor).  No atomics: two launches give the same bits.
+// The data gradient (eqa_conv3x3_dgrad) is a mode of the same kernel over dz with another tap-offset function; the filter gradient
+// stands in conv3x3_train.hip.
 #include "eqa_common.hpp"
 
 namespace {
@@ -68,7 +70,11 @@ struct C3Geom {
 };
 
 // x (N, H, W, Cin); Wpk (taps, Cin/16, Cout/32, 2, 64, 4); bias (Cout); res, y (P = N OH OW, Cout)
-template <int NT>
+// DG, the data gradient (eqa_conv3x3_dgrad): the same walk with the roles exchanged -- "x" is dz, "y" is dx, Wpk the flipped and
+// transposed pack, g.H x g.W the map that is READ (dz's), g.OH x g.OW the one that is written (dx's), no bias.  Tap (dy, dx) of
+// output pixel (iy, ix) reads dz at ((iy + dy - pad) / s, (ix + dx - pad) / s) where both divide and the quotients are inside; every
+// other tap -- three in four at stride 2 -- takes kOob like a tap on the padding.
+template <int NT, bool DG>
 __global__ __launch_bounds__(256, 1) void conv3x3_kernel(const float* __restrict__ x, const float* __restrict__ Wpk, const float* __restrict__ bias,
                                                          const float* __restrict__ res, float* __restrict__ y, int relu, int P, C3Geom g,
                                                          unsigned x_bytes, int n_ct, int total, int nwaves) {
@@ -106,16 +112,30 @@ __global__ __launch_bounds__(256, 1) void conv3x3_kernel(const float* __restrict
       const unsigned p = (unsigned)(t.row0 + 32 * m + j);
       const unsigned n = p / opix, r = p - n * opix;
       const unsigned oy = r / (unsigned)g.OW, ox = r - oy * (unsigned)g.OW;
-      const int iy0 = (int)oy * g.stride - g.pad, ix0 = (int)ox * g.stride - g.pad;
+      const int iy0 = (int)oy * (DG ? 1 : g.stride) - g.pad, ix0 = (int)ox * (DG ? 1 : g.stride) - g.pad;
       t.iy0[m] = p < (unsigned)P ? iy0 : -4;
       t.ix0[m] = ix0;
-      t.base[m] = (unsigned)(((int)n * g.H + iy0) * g.W + ix0) * (unsigned)Cin * 4u + 16u * (unsigned)h;
+      if constexpr (DG)       // the image's first pixel: the neighbour's own row and column come with the tap
+        t.base[m] = (unsigned)((int)n * g.H * g.W) * (unsigned)Cin * 4u + 16u * (unsigned)h;
+      else
+        t.base[m] = (unsigned)(((int)n * g.H + iy0) * g.W + ix0) * (unsigned)Cin * 4u + 16u * (unsigned)h;
     }
     return t;
   };
   // this lane's offsets of one tap: the neighbour's row where it is inside the lane's own image, kOob on the padding
   auto tap_off = [&](const Tile& t, int tap, unsigned& v0, unsigned& v1) {
     const int dy = tap / g.ksz, dx = tap - dy * g.ksz;
+    if constexpr (DG) {
+      const int sh = g.stride - 1, lo = g.stride - 1;      // stride 1 or 2: the quotient is a shift, the remainder a mask
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        const int ty = t.iy0[m] + dy, tx = t.ix0[m] + dx;  // (a negative one fails the unsigned comparison)
+        const bool in = !((ty | tx) & lo) && (unsigned)ty < (unsigned)(g.H << sh) && (unsigned)tx < (unsigned)(g.W << sh);
+        const unsigned off = t.base[m] + (unsigned)(((ty >> sh) * g.W + (tx >> sh)) * Cin) * 4u;
+        (m == 0 ? v0 : v1) = in ? off : kOob;
+      }
+      return;
+    }
     const unsigned d = (unsigned)((dy * g.W + dx) * Cin) * 4u;
     const bool in0 = (unsigned)(t.iy0[0] + dy) < (unsigned)g.H && (unsigned)(t.ix0[0] + dx) < (unsigned)g.W;
     const bool in1 = (unsigned)(t.iy0[1] + dy) < (unsigned)g.H && (unsigned)(t.ix0[1] + dx) < (unsigned)g.W;
@@ -180,7 +200,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_kernel(const float* __restrict
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           const int c = col0 + 32 * n + 8 * gq + 4 * h;                // < Cout, a multiple of 4
-          const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + c);
+          f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (!DG) bv = *reinterpret_cast<const f32x4*>(bias + c);
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
             // (the row subtile's offset rides in the lane offset, which the range check certainly covers)
@@ -251,9 +272,43 @@ int eqa_conv3x3_nhwc(const float* x, const float* Wpk, const float* bias, const 
   const dim3 grid((unsigned)(nwaves / 4));
   hipStream_t st = (hipStream_t)stream;
   if (NT == 2)
-    hipLaunchKernelGGL(conv3x3_kernel<2>, grid, dim3(256), 0, st, x, Wpk, bias, res, y, relu, (int)P, g, x_bytes, n_ct, (int)total, nwaves);
+    hipLaunchKernelGGL((conv3x3_kernel<2, false>), grid, dim3(256), 0, st, x, Wpk, bias, res, y, relu, (int)P, g, x_bytes, n_ct, (int)total, nwaves);
   else
-    hipLaunchKernelGGL(conv3x3_kernel<1>, grid, dim3(256), 0, st, x, Wpk, bias, res, y, relu, (int)P, g, x_bytes, n_ct, (int)total, nwaves);
+    hipLaunchKernelGGL((conv3x3_kernel<1, false>), grid, dim3(256), 0, st, x, Wpk, bias, res, y, relu, (int)P, g, x_bytes, n_ct, (int)total, nwaves);
+  return launch_status();
+}
+
+int eqa_conv3x3_dgrad_supported(long long N, int H, int W, int Cin, int Cout, int taps, int stride) {
+  return eqa_conv3x3_supported(N, H, W, Cin, Cout, taps, stride);      // dx is x's size, dz is y's
+}
+
+int eqa_conv3x3_dgrad(const float* dz, const float* Wdpk, const float* res, float* dx, long long N, int H, int W, int Cin, int Cout, int taps,
+                      int stride, void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return EQA_ERR_INVALID_ARG;
+  if (!eqa_conv3x3_supported(N, H, W, Cin, Cout, taps, stride)) return EQA_ERR_UNSUPPORTED;
+  if (N == 0) return EQA_OK;
+  if (!dz || !Wdpk || !dx) return EQA_ERR_INVALID_ARG;
+  if (dx == dz || dx == res) return EQA_ERR_INVALID_ARG;
+  if ((((uintptr_t)dz | (uintptr_t)Wdpk | (uintptr_t)res | (uintptr_t)dx) & 15)) return EQA_ERR_UNSUPPORTED;
+  C3Geom g;                                                 // the kernel's roles: it reads dz (Cout channels), writes dx (Cin)
+  g.ksz = taps == 9 ? 3 : 1;
+  g.pad = taps == 9 ? 1 : 0;
+  g.H = (int)c3_out(H, g.ksz, g.pad, stride);
+  g.W = (int)c3_out(W, g.ksz, g.pad, stride);
+  g.OH = H, g.OW = W, g.Cin = Cout, g.Cout = Cin, g.stride = stride;
+  const long long P = N * H * W;                            // P * Cin * 4 < 2^32
+  const unsigned dz_bytes = (unsigned)((unsigned long long)N * g.H * g.W * Cout * 4ULL);
+  const int NT = Cin % 64 == 0 ? 2 : 1;
+  const long long n_rt = (P + 63) / 64;
+  const int n_ct = Cin / (32 * NT);
+  const long long total = n_rt * n_ct;                      // < 2^31
+  const int nwaves = (int)std::min<long long>(1024, (total + 3) / 4 * 4);
+  const dim3 grid((unsigned)(nwaves / 4));
+  hipStream_t st = (hipStream_t)stream;
+  if (NT == 2)
+    hipLaunchKernelGGL((conv3x3_kernel<2, true>), grid, dim3(256), 0, st, dz, Wdpk, nullptr, res, dx, 0, (int)P, g, dz_bytes, n_ct, (int)total, nwaves);
+  else
+    hipLaunchKernelGGL((conv3x3_kernel<1, true>), grid, dim3(256), 0, st, dz, Wdpk, nullptr, res, dx, 0, (int)P, g, dz_bytes, n_ct, (int)total, nwaves);
   return launch_status();
 }
 

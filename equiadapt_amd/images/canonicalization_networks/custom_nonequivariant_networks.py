@@ -2,7 +2,8 @@
 
 Reference: equiadapt/images/canonicalization_networks/custom_nonequivariant_networks.py:8-130.
 Small MIOpen convolutions (PyTorch-ROCm); module / parameter names match the reference's state_dict.
-ResNet18Network's eval forward runs 19 of its 20 convolutions on eqa_conv3x3_nhwc (csrc/conv3x3.hip).
+ResNet18Network's eval forward runs 19 of its 20 convolutions on eqa_conv3x3_nhwc (csrc/conv3x3.hip); with EQA_RESNET_TRAIN_KERNEL=1
+its training step runs them on that kernel, its two gradients and the eqa_bn_res_act_* block (csrc/conv3x3_train.hip).
 The wide torchvision wrappers (WideResNet50Network, WideResNet101Network) are out of scope.
 """
 import os
@@ -13,6 +14,7 @@ import torch
 from torch import nn
 
 from equiadapt_amd.common.derived import DerivedCache, bn_eval_affine
+from equiadapt_amd.common.utils import mark_written
 
 
 _BN_FLAG_LOCK = threading.Lock()
@@ -299,6 +301,116 @@ class ConvNetwork(nn.Module):
         return self.final_fc(self.enc_network(x).reshape(x.shape[0], -1))
 
 
+class _BranchGrad:
+    """The gradient of one branch of a basic block at the block's input, handed from the backward that makes it (the second
+    batch-norm's residual, or the projection's data gradient) to the first convolution's data gradient, which adds it in its
+    epilogue: the sum of the two branches costs no pass of its own.  The receiver's node depends on the giver's through the block, so
+    the giver has always run; a hand-over that does not find its other end raises, it never drops a gradient."""
+
+    def __init__(self):
+        self.grad: Optional[torch.Tensor] = None
+
+    def give(self, grad: torch.Tensor) -> None:
+        if self.grad is not None:
+            raise RuntimeError("ResNet18Network: a branch gradient was handed over twice before the block's first convolution took it")
+        self.grad = grad
+
+    def take(self) -> torch.Tensor:
+        grad, self.grad = self.grad, None
+        if grad is None:
+            raise RuntimeError("ResNet18Network: the block's first convolution ran its backward before the other branch's gradient was there")
+        return grad
+
+
+class Conv3x3Function(torch.autograd.Function):
+    """z = conv(x) of a basic block's 3 x 3 layer or 1 x 1 stride-2 shortcut on a (N, H, W, Cin) map (eqa_conv3x3_nhwc with a zero
+    bias, no residual, no ReLU: in training the batch-norm behind it needs z itself), with its gradients, each only where it is
+    needed: dW from eqa_conv3x3_wgrad, dx from eqa_conv3x3_dgrad -- or, with `wgrad_kernel` / `dgrad_kernel` false, the library's
+    gradient on the same memory.  `take`: a _BranchGrad whose gradient is added to dx (in the kernel's epilogue); `give`: one that
+    receives dx, autograd then being told that x has no gradient from here.  The caller has asked the three `ops.conv3x3*_supported`
+    queries."""
+
+    @staticmethod
+    def forward(ctx, x, weight, taps, stride, zero_bias, wgrad_kernel=True, dgrad_kernel=True, take=None, give=None):
+        from equiadapt_amd import ops
+
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.geom = (taps, stride, wgrad_kernel, dgrad_kernel, take, give)
+        return ops.conv3x3_nhwc(x, ops.pack_conv3x3_weights(weight.detach()), zero_bias, None, False, taps, stride)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz):
+        from equiadapt_amd import ops
+
+        x, weight = ctx.saved_tensors
+        taps, stride, wgrad_kernel, dgrad_kernel, take, give = ctx.geom
+        dz = dz.contiguous()
+        dx = dw = None
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        mask = (need_dx and not dgrad_kernel, need_dw and not wgrad_kernel, False)
+        if mask[0] or mask[1]:
+            pad = 1 if taps == 9 else 0
+            dx, dw, _ = torch.ops.aten.convolution_backward(dz.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), weight, None, (stride, stride),
+                                                            (pad, pad), (1, 1), False, (0, 0), 1, mask)
+            if mask[0]:
+                dx = dx.permute(0, 2, 3, 1)
+                if take is not None:
+                    dx = dx + take.take()
+        if need_dw and wgrad_kernel:
+            dw = ops.conv3x3_wgrad(x, dz, taps, stride)
+        if need_dx and dgrad_kernel:
+            dx = ops.conv3x3_dgrad(dz, ops.pack_conv3x3_dgrad_weights(weight.detach()), (x.shape[1], x.shape[2]),
+                                   None if take is None else take.take(), taps, stride)
+        if need_dx and give is not None:
+            give.give(dx)
+            dx = None
+        return dx, dw, None, None, None, None, None, None, None
+
+
+class BnResActFunction(torch.autograd.Function):
+    """y = [relu](bn(z) [+ res]) with batch statistics on a (N, H, W, C) map -- the three forms of a basic block in training:
+    relu(bn1(z)), relu(bn2(z) + shortcut), bn(z) on the projection -- on eqa_bn_act_stats / eqa_bn_act_finalize (which update the
+    module's running statistics as nn.BatchNorm2d does) and eqa_bn_res_act_fwd; backward eqa_bn_res_act_bwd_reduce /
+    eqa_bn_act_bwd_finalize / eqa_bn_res_act_bwd_apply -> gradients of z, gamma, beta and res.  `give`: a _BranchGrad that receives
+    the residual's gradient instead of autograd."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, bn, res=None, relu=True, give=None):
+        from equiadapt_amd import ops
+
+        C = z.shape[-1]
+        z = z.contiguous()
+        z2 = z.view(-1, C)
+        res2 = None if res is None else res.contiguous().view(-1, C)
+        scale, shift, mean, rstd = ops.bn_fold_batch_stats(z2, bn)
+        y = ops.bn_res_act_fwd(z2, scale, shift, res2, relu).view(z.shape)
+        ctx.save_for_backward(z, scale, shift, mean, rstd, gamma, *(() if res is None else (res2,)))
+        ctx.form = (relu, give)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from equiadapt_amd import ops
+
+        z, scale, shift, mean, rstd, gamma = ctx.saved_tensors[:6]
+        res2 = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        relu, give = ctx.form
+        C = z.shape[-1]
+        need_dres = res2 is not None and (give is not None or ctx.needs_input_grad[4])
+        dz, dgamma, dbeta, dres = ops.bn_res_act_bwd(gy.contiguous().view(-1, C), z.view(-1, C), scale, shift, mean, rstd, gamma.detach(), res2,
+                                                     relu, need_dres)
+        if dres is not None:
+            dres = dres.view(z.shape)
+            if give is not None:
+                give.give(dres)
+                dres = None
+        return (dz.view(z.shape), dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None, dres, None,
+                None)
+
+
 class _BasicBlock(nn.Module):
     """The basic residual block of the published ResNet-18 (He et al. 2015, table 1, with the stride on the first 3 x 3 layer and a
     1 x 1 projection shortcut where the shape changes): relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut(x))."""
@@ -371,6 +483,14 @@ class ResNet18Network(nn.Module):
               the library (wide 3 x 3 layers at 2048 output pixels and more, where the library was measured faster), runs F.conv2d on
               the same channels-last memory + add_ + relu_ ("lib").  The tail is the mean over the pixels and F.linear.  No host
               synchronisation: the step can be captured into a hipGraph.
+      train   opt-in, `EQA_RESNET_TRAIN_KERNEL=1` (read per forward; the default training route stays plain): the module and all its
+              batch-norms in train(), affine and tracking running statistics, and the fused rule's conditions on input, parameters
+              and hooks.  The stem runs through torch autograd on a channels-last input ("lib:train"); behind it every convolution
+              is Conv3x3Function ("conv3x3:train", "conv1x1s2:train": eqa_conv3x3_nhwc forward, eqa_conv3x3_wgrad / eqa_conv3x3_dgrad
+              backward, each gradient on the library instead where its gate on shapes says so: `last_wgrad_routes`) and every
+              batch-norm BnResActFunction (batch statistics, the residual and the ReLU inside; running statistics updated as
+              nn.BatchNorm2d does); a layer the queries refuse or `_kernel_pays` hands over runs F.conv2d under autograd
+              ("lib:train").  The sum of the two branch gradients at a block's input rides in the first convolution's data gradient.
     """
 
     def __init__(self, in_shape: tuple, out_channels: int, kernel_size: int, num_layers: int = 2, out_vector_size: int = 128):
@@ -378,6 +498,7 @@ class ResNet18Network(nn.Module):
         self.resnet18 = _ResNet18(out_vector_size)
         self.out_vector_size = out_vector_size
         self.last_routes: List[str] = []
+        self.last_wgrad_routes: List[str] = []     # per convolution, where its filter gradient runs on the training route: "kernel" / "lib"
         self._cache = DerivedCache()
 
     def load_torchvision_state_dict(self, state_dict) -> None:
@@ -404,11 +525,21 @@ class ResNet18Network(nn.Module):
     def _fused_applies(self, x: torch.Tensor) -> bool:
         if self.training or torch.is_grad_enabled() or os.environ.get("EQA_RESNET_KERNEL", "1") == "0":
             return False
+        return self._kernels_take(x, training=False)
+
+    def _train_applies(self, x: torch.Tensor) -> bool:
+        if not self.training or os.environ.get("EQA_RESNET_TRAIN_KERNEL", "0") != "1" or os.environ.get("EQA_RESNET_KERNEL", "1") == "0":
+            return False
+        return self._kernels_take(x, training=True)
+
+    def _kernels_take(self, x: torch.Tensor, training: bool) -> bool:
+        """What both kernel routes ask of the input, the parameters and the submodules; every batch-norm in the route's own mode."""
         if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and x.shape[0] >= 1):
             return False
         lin = self.resnet18.fc[0]
         for m in [m for pair in self._pairs() for m in pair] + [lin]:
-            if isinstance(m, nn.BatchNorm2d) and (m.training or m.running_mean is None or not m.affine):
+            if isinstance(m, nn.BatchNorm2d) and (m.training != training or m.running_mean is None or not m.affine
+                                                  or (training and not m.track_running_stats)):
                 return False
             for t in list(m._parameters.values()) + list(m._buffers.values()):
                 if t is None or t.dtype == torch.int64:          # (an absent bias; num_batches_tracked)
@@ -480,8 +611,84 @@ class ResNet18Network(nn.Module):
         lin = net.fc[0]
         return torch.nn.functional.linear(h.mean(dim=(1, 2)), lin.weight, lin.bias)
 
+    @staticmethod
+    def _wgrad_pays(pixels: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+        """The filter gradient's own gate on shapes alone (measured: DESIGN.md section 1, "ResNet18Network", the training tables): at
+        2304 output pixels and more the library's weight gradient was faster on all seven 3 x 3 forms and slower on the three 1 x 1
+        shortcuts.  Below 2048 pixels nothing was measured, and the kernel keeps the layer."""
+        return not (taps == 9 and pixels >= 2048)
+
+    @staticmethod
+    def _dgrad_pays(pixels: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+        """The data gradient's gate, likewise: at 2304 output pixels and more the library's was faster on all ten forms (at stride 2
+        by 3 x: three taps in four are dropped loads whose matrix instructions still run)."""
+        return pixels < 2048
+
+    @staticmethod
+    def _out_pixels(h: torch.Tensor, conv: nn.Conv2d) -> int:
+        k, stride, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        return h.shape[0] * ((h.shape[1] + 2 * pad - k) // stride + 1) * ((h.shape[2] + 2 * pad - k) // stride + 1)
+
+    def _train_kernel_takes(self, h: torch.Tensor, conv: nn.Conv2d) -> bool:
+        from equiadapt_amd import ops
+
+        k, stride = conv.kernel_size[0], conv.stride[0]
+        shape = (h.shape[0], h.shape[1], h.shape[2], conv.in_channels, conv.out_channels, k * k, stride)
+        return (ops.conv3x3_supported(*shape) and ops.conv3x3_dgrad_supported(*shape) and ops.conv3x3_wgrad_supported(*shape)
+                and self._kernel_pays(self._out_pixels(h, conv), conv.in_channels, k * k, stride))
+
+    def _train_layer(self, h, conv, bn, res, relu, slot, zero_bias, take=None, give=None, res_give=None):
+        """One convolution + batch-norm with batch statistics (+ residual) (+ ReLU) on the (B, h, w, C) map `h` under autograd:
+        Conv3x3Function where the kernels take the shape and pay, else the library's convolution on the same memory ("lib:train");
+        BnResActFunction behind either."""
+        taps, stride = conv.kernel_size[0] ** 2, conv.stride[0]
+        if self._train_kernel_takes(h, conv):
+            shape = (self._out_pixels(h, conv), conv.in_channels, conv.out_channels, taps, stride)
+            wk, dk = self._wgrad_pays(*shape), self._dgrad_pays(*shape)
+            self.last_routes[slot] = "conv1x1s2:train" if taps == 1 else "conv3x3:train"
+            self.last_wgrad_routes[slot] = "kernel" if wk else "lib"
+            z = Conv3x3Function.apply(h, conv.weight, taps, stride, zero_bias[:conv.out_channels], wk, dk, take, give)
+        else:
+            assert take is None and give is None
+            self.last_routes[slot] = "lib:train"
+            self.last_wgrad_routes[slot] = "lib"
+            z = torch.nn.functional.conv2d(h.permute(0, 3, 1, 2), conv.weight, None, conv.stride, conv.padding).permute(0, 2, 3, 1)
+        return BnResActFunction.apply(z, bn.weight, bn.bias, bn, res, relu, res_give)
+
+    def _forward_train(self, x: torch.Tensor) -> torch.Tensor:
+        net = self.resnet18
+        self.last_routes = ["lib:train"] + [""] * 19
+        self.last_wgrad_routes = ["lib"] + [""] * 19
+        # The library's batch-norm writes its running statistics without moving their version counter, which the eval route's cache of
+        # folded filters is keyed on (measured: the next fused forward ran on the stem's statistics from before the step).  The
+        # counter moves BEFORE the call: the library keeps the two buffers for its backward, and autograd checks their version there.
+        mark_written(net.bn1.running_mean, net.bn1.running_var)
+        h = net.maxpool(net.relu(net.bn1(net.conv1(x.contiguous(memory_format=torch.channels_last))))).permute(0, 2, 3, 1)
+        if not h.is_contiguous():
+            h = h.contiguous()
+        zero_bias = torch.zeros(512, dtype=torch.float32, device=x.device)
+        slot = 1
+        for blk in self._blocks():
+            proj = blk.downsample
+            # the shortcut's gradient at the block input rides in conv1's data gradient where both ends are kernels
+            hint = None
+            if h.requires_grad and self._train_kernel_takes(h, blk.conv1) and (proj is None or self._train_kernel_takes(h, proj[0])):
+                hint = _BranchGrad()
+            t = self._train_layer(h, blk.conv1, blk.bn1, None, True, slot, zero_bias, take=hint)
+            if proj is not None:
+                sc = self._train_layer(h, proj[0], proj[1], None, False, slot + 2, zero_bias, give=hint)
+                h = self._train_layer(t, blk.conv2, blk.bn2, sc, True, slot + 1, zero_bias)
+            else:
+                h = self._train_layer(t, blk.conv2, blk.bn2, h, True, slot + 1, zero_bias, res_give=hint)
+            slot += 2 if proj is None else 3
+        lin = net.fc[0]
+        return torch.nn.functional.linear(h.mean(dim=(1, 2)), lin.weight, lin.bias)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._fused_applies(x):
             return self._forward_fused(x)
+        self.last_wgrad_routes = []
+        if self._train_applies(x):
+            return self._forward_train(x)
         self.last_routes = ["plain"] * 20
         return self.resnet18(x)

@@ -1736,3 +1736,135 @@ def conv3x3_nhwc(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, res: Op
                                   stride, _stream())
     _lib.check(st, "eqa_conv3x3_nhwc")
     return y
+
+
+def _conv3x3_geom(h: int, w: int, taps: int, stride: int) -> Tuple[int, int, int, int]:
+    k, pad = (3, 1) if taps == 9 else (1, 0)
+    return k, pad, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+
+
+def _conv3x3_map(t: torch.Tensor, what: str, name: str) -> torch.Tensor:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()):
+        raise RuntimeError(f"{what}: {name} must be a contiguous (N, H, W, C) fp32 map on the device")
+    return t
+
+
+def conv3x3_wgrad_supported(n: int, h: int, w: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+    """Shapes and sizes eqa_conv3x3_wgrad takes -- what `conv3x3_supported` admits, the size test included."""
+    return bool(_lib.load().eqa_conv3x3_wgrad_supported(n, h, w, cin, cout, taps, stride))
+
+
+def conv3x3_wgrad(x: torch.Tensor, dz: torch.Tensor, taps: int = 9, stride: int = 1) -> torch.Tensor:
+    """Filter gradient of z = conv3x3_nhwc(x) for the output gradient dz (eqa_conv3x3_wgrad: the contraction over the output pixels
+    on the fp32 MFMA, split over the chip's waves, partial tiles added in a fixed order in fp64).  x: a contiguous (N, H, W, Cin)
+    map, dz: (N, OH, OW, Cout) -> dW (Cout, Cin, k, k), the layout of `conv.weight`.  No autograd."""
+    lib = _lib.load()
+    x, dz = _conv3x3_map(x, "conv3x3_wgrad", "x"), _conv3x3_map(dz, "conv3x3_wgrad", "dz")
+    N, H, W, Cin = x.shape
+    Cout = dz.shape[3]
+    if not conv3x3_wgrad_supported(N, H, W, Cin, Cout, taps, stride):
+        raise _lib.EqaLibraryError(f"eqa_conv3x3_wgrad does not take {N} x {H} x {W} maps of {Cin} -> {Cout} channels with taps {taps}, "
+                                   f"stride {stride} (ask conv3x3_wgrad_supported first)")
+    k, _, OH, OW = _conv3x3_geom(H, W, taps, stride)
+    if dz.device != x.device or tuple(dz.shape) != (N, OH, OW, Cout):
+        raise ValueError(f"conv3x3_wgrad: dz must be a {(N, OH, OW, Cout)} map on x's device, got {tuple(dz.shape)}")
+    dW = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
+    nbytes = lib.eqa_conv3x3_wgrad_workspace_bytes(N, H, W, Cin, Cout, taps, stride)
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("conv3x3_wgrad"):
+        st = lib.eqa_conv3x3_wgrad(x.data_ptr(), dz.data_ptr(), work.data_ptr() if nbytes else None, dW.data_ptr(), N, H, W, Cin, Cout,
+                                   taps, stride, _stream())
+    _lib.check(st, "eqa_conv3x3_wgrad")
+    return dW
+
+
+def conv3x3_dgrad_supported(n: int, h: int, w: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+    """Shapes and sizes eqa_conv3x3_dgrad takes (n, h, w: the INPUT map's, as for the forward) -- what `conv3x3_supported` admits."""
+    return bool(_lib.load().eqa_conv3x3_dgrad_supported(n, h, w, cin, cout, taps, stride))
+
+
+def pack_conv3x3_dgrad_weights(w: torch.Tensor) -> torch.Tensor:
+    """(Cout, Cin, k, k) filters, k in {1, 3}, Cin and Cout multiples of 32 -> the operand of eqa_conv3x3_dgrad: input and output
+    channels exchanged, the taps flipped, in the forward's fragment order, shape (k k, Cout/16, Cin/32, 2, 64, 4):
+        Wdpk[k dy + dx][s][n][b][32 h + i][t] = w[16 s + 8 b + 4 h + t][32 n + i][k - 1 - dy][k - 1 - dx]
+    (`pack_conv3x3_weights` of the flipped transpose).  A pure torch op: it works on any device."""
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.shape[2] not in (1, 3) or w.shape[0] % 32 or w.shape[1] % 32 or not w.numel():
+        raise ValueError(f"pack_conv3x3_dgrad_weights takes (Cout, Cin, k, k) filters, k in (1, 3), channels on multiples of 32, got {tuple(w.shape)}")
+    return pack_conv3x3_weights(w.transpose(0, 1).flip(2, 3))
+
+
+def conv3x3_dgrad(dz: torch.Tensor, wdpk: torch.Tensor, in_hw: Tuple[int, int], res: Optional[torch.Tensor] = None, taps: int = 9,
+                  stride: int = 1) -> torch.Tensor:
+    """Data gradient of z = conv3x3_nhwc(x) (+ res) in one launch (eqa_conv3x3_dgrad, a mode of the forward kernel): dz a contiguous
+    (N, OH, OW, Cout) map, wdpk = pack_conv3x3_dgrad_weights(filters), in_hw = (H, W) of x (OH does not determine H at stride 2);
+    res and the result (N, H, W, Cin) -- res is the other branch's gradient at the block input.  No autograd."""
+    lib = _lib.load()
+    dz = _conv3x3_map(dz, "conv3x3_dgrad", "dz")
+    wdpk = _need(wdpk, "wdpk")
+    if wdpk.dim() != 6 or wdpk.shape[0] != taps or tuple(wdpk.shape[3:]) != (2, 64, 4) or wdpk.shape[1] * 16 != dz.shape[3]:
+        raise ValueError(f"conv3x3_dgrad: wdpk must be pack_conv3x3_dgrad_weights' ({taps}, Cout/16, Cin/32, 2, 64, 4) operand for "
+                         f"{dz.shape[3]} output channels, got {tuple(wdpk.shape)}")
+    Cout, Cin = wdpk.shape[1] * 16, wdpk.shape[2] * 32
+    N, (H, W) = dz.shape[0], in_hw
+    if not conv3x3_dgrad_supported(N, H, W, Cin, Cout, taps, stride):
+        raise _lib.EqaLibraryError(f"eqa_conv3x3_dgrad does not take {N} x {H} x {W} maps of {Cin} -> {Cout} channels with taps {taps}, "
+                                   f"stride {stride} (ask conv3x3_dgrad_supported first)")
+    _, _, OH, OW = _conv3x3_geom(H, W, taps, stride)
+    if tuple(dz.shape[1:3]) != (OH, OW):
+        raise ValueError(f"conv3x3_dgrad: a {H} x {W} input gives a {OH} x {OW} output, dz is {tuple(dz.shape)}")
+    p_res = None
+    if res is not None:
+        if res.dtype != torch.float32 or res.device != dz.device or tuple(res.shape) != (N, H, W, Cin) or not res.is_contiguous():
+            raise RuntimeError(f"conv3x3_dgrad: res must be a contiguous fp32 {(N, H, W, Cin)} map on dz's device")
+        p_res = res.data_ptr()
+    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dz.device)
+    with torch.cuda.device(dz.device), _timed("conv3x3_dgrad"):
+        st = lib.eqa_conv3x3_dgrad(dz.data_ptr(), wdpk.data_ptr(), p_res, dx.data_ptr(), N, H, W, Cin, Cout, taps, stride, _stream())
+    _lib.check(st, "eqa_conv3x3_dgrad")
+    return dx
+
+
+def bn_res_act_fwd(z: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, res: Optional[torch.Tensor], relu: bool) -> torch.Tensor:
+    """y = [relu](fmaf(scale[c], z, shift[c]) [+ res]) on a channels-last (npix, C) view (eqa_bn_res_act_fwd)."""
+    lib = _lib.load()
+    z, scale, shift = _need(z, "z"), _need(scale, "scale"), _need(shift, "shift")
+    res, p_res = _opt(res, "res", torch.float32)
+    if res is not None and res.shape != z.shape:
+        raise ValueError(f"bn_res_act_fwd: res is {tuple(res.shape)}, z {tuple(z.shape)}")
+    npix, C = z.shape
+    y = torch.empty_like(z)
+    with torch.cuda.device(z.device), _timed("bn_res_act_fwd"):
+        st = lib.eqa_bn_res_act_fwd(z.data_ptr(), scale.data_ptr(), shift.data_ptr(), p_res, int(relu), y.data_ptr(), npix, C, _stream())
+    _lib.check(st, "eqa_bn_res_act_fwd")
+    return y
+
+
+def bn_res_act_bwd(gy: torch.Tensor, z: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor,
+                   gamma: torch.Tensor, res: Optional[torch.Tensor], relu: bool, need_dres: bool = False):
+    """Backward of batch-norm (batch statistics) + residual + ReLU on (npix, C): -> (dz, dgamma, dbeta, dres); dres (= the masked
+    gy, written by the pass that writes dz) is None unless `need_dres` (eqa_bn_res_act_bwd_reduce / eqa_bn_act_bwd_finalize /
+    eqa_bn_res_act_bwd_apply)."""
+    lib = _lib.load()
+    gy, z = _need(gy, "gy"), _need(z, "z")
+    res, p_res = _opt(res, "res", torch.float32)
+    npix, C = z.shape
+    if gy.shape != z.shape or (res is not None and res.shape != z.shape):
+        raise ValueError(f"bn_res_act_bwd: gy, z and res must be of one shape, got {tuple(gy.shape)}, {tuple(z.shape)}")
+    part = torch.empty((max(lib.eqa_bn_act_partial_blocks(npix), 1), C, 2), dtype=torch.float64, device=z.device)
+    with torch.cuda.device(z.device), _timed("bn_res_act_bwd_reduce"):
+        st = lib.eqa_bn_res_act_bwd_reduce(gy.data_ptr(), z.data_ptr(), scale.data_ptr(), shift.data_ptr(), p_res, int(relu), mean.data_ptr(),
+                                           rstd.data_ptr(), part.data_ptr(), npix, C, _stream())
+    _lib.check(st, "eqa_bn_res_act_bwd_reduce")
+    coef = torch.empty((5, C), dtype=torch.float32, device=z.device)          # dgamma, dbeta, gscale, m1, m2
+    with torch.cuda.device(z.device):
+        st = lib.eqa_bn_act_bwd_finalize(part.data_ptr(), npix, C, gamma.data_ptr(), rstd.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
+                                         coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr(), _stream())
+    _lib.check(st, "eqa_bn_act_bwd_finalize")
+    dz = torch.empty_like(z)
+    dres = torch.empty_like(z) if need_dres else None
+    with torch.cuda.device(z.device), _timed("bn_res_act_bwd_apply"):
+        st = lib.eqa_bn_res_act_bwd_apply(gy.data_ptr(), z.data_ptr(), scale.data_ptr(), shift.data_ptr(), p_res, int(relu), mean.data_ptr(),
+                                          rstd.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr(), dz.data_ptr(),
+                                          dres.data_ptr() if need_dres else None, npix, C, _stream())
+    _lib.check(st, "eqa_bn_res_act_bwd_apply")
+    return dz, coef[0], coef[1], dres

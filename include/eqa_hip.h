@@ -1046,6 +1046,61 @@ int eqa_conv3x3_supported(long long N, int H, int W, int Cin, int Cout, int taps
 int eqa_conv3x3_nhwc(const float* x, const float* Wpk, const float* bias, const float* res, int relu, float* y, long long N, int H, int W,
                      int Cin, int Cout, int taps, int stride, void* stream);
 
+/*
+ * The gradients of eqa_conv3x3_nhwc (no bias gradient: the network's convolutions have none), same geometry, same admitted shapes
+ * (eqa_conv3x3_wgrad_supported and eqa_conv3x3_dgrad_supported admit exactly what eqa_conv3x3_supported admits, the size test
+ * included).  x:(N,H,W,Cin), dz:(N,OH,OW,Cout).
+ *
+ * Filter gradient (csrc/conv3x3_train.hip), the contraction over the P = N OH OW output pixels on v_mfma_f32_32x32x2_f32:
+ *   dW[o][c][dy][dx] = sum_{n,oy,ox} dz[n][oy][ox][o] x[n][s oy + dy - pad][s ox + dx - pad][c]      (taps on the padding add 0)
+ * dW:(Cout,Cin,k,k) fp32 contiguous, the layout of the convolution's filters.  The pixel range is split over the chip's waves;
+ * every wave writes a partial tile to workspace (eqa_conv3x3_wgrad_workspace_bytes bytes, a function of the sizes alone; 0 for
+ * N = 0 and for sizes the query refuses) and a second launch adds the partials in a fixed order in fp64: no atomics, two calls on
+ * the same operands give the same bits.  Nothing outside x and dz is read.  N = 0: nothing is launched, dW is zeroed (workspace may
+ * be NULL).  A refused size: EQA_ERR_UNSUPPORTED before any pointer is looked at.  NULL pointers, equal base pointers among x, dz,
+ * workspace and dW: EQA_ERR_INVALID_ARG (buffers that overlap otherwise are the caller's error).  Pointers not 16-byte aligned:
+ * EQA_ERR_UNSUPPORTED.
+ *
+ * Data gradient, a mode of the forward kernel (csrc/conv3x3.hip) over dz:
+ *   dx[n][iy][ix][c] = sum over (ey, ex, o) with (iy + pad - ey) and (ix + pad - ex) divisible by s, quotients inside (OH, OW), of
+ *                        dz[n][(iy + pad - ey) / s][(ix + pad - ex) / s][o] W[o][c][ey][ex]     (+ res[n][iy][ix][c])
+ * Every element of dx:(N,H,W,Cin) is written -- a pixel no tap reaches gets res or 0 --; H and W are arguments because OH does not
+ * determine H at stride 2.  res:(N,H,W,Cin) or NULL: the other branch's gradient at the block input.  Wdpk: the filters with input
+ * and output channels exchanged and the taps flipped, in the forward's fragment order (ops.pack_conv3x3_dgrad_weights),
+ *   Wdpk[k dy + dx][s][n][b][32 h + i][t] = W[16 s + 8 b + 4 h + t][32 n + i][k-1-dy][k-1-dx]     (taps, Cout/16, Cin/32, 2, 64, 4)
+ * At stride 2 three taps in four are dropped loads whose matrix instructions still run.  Errors and determinism as the forward's:
+ * a refused shape EQA_ERR_UNSUPPORTED before any pointer is read; NULL dz, Wdpk or dx, or dx equal to dz or res:
+ * EQA_ERR_INVALID_ARG; pointers 16-byte aligned (else EQA_ERR_UNSUPPORTED); N = 0: nothing is launched.
+ * Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_conv3x3_wgrad_supported(long long N, int H, int W, int Cin, int Cout, int taps, int stride);
+long long eqa_conv3x3_wgrad_workspace_bytes(long long N, int H, int W, int Cin, int Cout, int taps, int stride);
+int eqa_conv3x3_wgrad(const float* x, const float* dz, void* workspace, float* dW, long long N, int H, int W, int Cin, int Cout, int taps,
+                      int stride, void* stream);
+int eqa_conv3x3_dgrad_supported(long long N, int H, int W, int Cin, int Cout, int taps, int stride);
+int eqa_conv3x3_dgrad(const float* dz, const float* Wdpk, const float* res, float* dx, long long N, int H, int W, int Cin, int Cout, int taps,
+                      int stride, void* stream);
+
+/*
+ * Batch-norm (given per-channel scale / shift) with the residual inside and an optional ReLU, on channels-last (npix, C) views with
+ * C % 4 == 0 (csrc/conv3x3_train.hip) -- the three forms of a basic block in training: relu(bn(z)), relu(bn(z) + res), bn(z):
+ *   t = fmaf(scale[c], z, shift[c]) (+ res),   y = relu ? max(t, 0) : t                        res NULL: no residual
+ * Backward in the two passes of eqa_bn_act_bwd_*: with g = relu ? gy [t > 0] : gy -- t recomputed by the forward's very expression,
+ * so the mask is the forward's mask -- eqa_bn_res_act_bwd_reduce writes the per-block fp64 partials of sum(g) and sum(g zhat),
+ * zhat = (z - mean) rstd, in the layout eqa_bn_act_bwd_finalize reads (partial: eqa_bn_act_partial_blocks(npix) * C * 2 doubles), and
+ * eqa_bn_res_act_bwd_apply writes dz = gscale (g - m1 - zhat m2) and, where dres is not NULL, dres = g in the same pass.  The batch
+ * statistics and both finalisations are eqa_bn_act_stats / eqa_bn_act_finalize / eqa_bn_act_bwd_finalize, unchanged.
+ * npix = 0: nothing is launched.  NULL required pointers: EQA_ERR_INVALID_ARG; C % 4 != 0 or pointers not 16-byte aligned:
+ * EQA_ERR_UNSUPPORTED.  Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_bn_res_act_fwd(const float* z, const float* scale, const float* shift, const float* res, int relu, float* y, int64_t npix, int C,
+                       void* stream);
+int eqa_bn_res_act_bwd_reduce(const float* gy, const float* z, const float* scale, const float* shift, const float* res, int relu,
+                              const float* mean, const float* rstd, double* partial, int64_t npix, int C, void* stream);
+int eqa_bn_res_act_bwd_apply(const float* gy, const float* z, const float* scale, const float* shift, const float* res, int relu,
+                             const float* mean, const float* rstd, const float* gscale, const float* m1, const float* m2, float* dz,
+                             float* dres, int64_t npix, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

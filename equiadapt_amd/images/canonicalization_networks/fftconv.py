@@ -44,6 +44,11 @@ AUTO_MIN_CIN = int(os.environ.get("EQA_FFT_GEMM_AUTO_MIN_CIN", "128"))
 # scaled, so it runs only where the producer of V hands over a bound of |V| on the device: the fused lifting kernel on non-negative
 # (relu) activations, whose DC bins bound every other bin (eqa_lift5_fft48k5_input_dcmax).  Everywhere else "auto" stays as above.
 AUTO_MIN_CIN_H3 = int(os.environ.get("EQA_FFT_GEMM_AUTO_MIN_CIN_H3", "64"))
+# Which matrix instruction "h3" runs on: "32" = v_mfma_f32_32x32x16_f16 (eqa_fft48k5_cgemm3m_f16x2, K-stages of 16), "16" =
+# v_mfma_f32_16x16x32_f16 (eqa_fft48k5_cgemm3m_f16x2_k32, K-stages of 32: round 27).  Same operands, split and products; the low bits
+# of the result differ (32 k per accumulator rounding instead of 16).  The A/B switch of profiles/r27.
+H3_MFMA = os.environ.get("EQA_FFT_GEMM_H3_MFMA", "16")
+LAST_H3_MFMA = None     # ... and which of the two the most recent "h3" contraction ran on
 DCMAX_SLOTS = 256       # EQA_LIFT5_DCMAX_SLOTS (include/eqa_hip.h)
 LAST_FORM = None        # the form the most recent `contract` on the hand-written GEMM ran in (bench.py reports it)
 # Channel counts the kernels above do not take but that are multiples of 16 (144 = 16 fields x 9 of the steerable network, 288, 48,
@@ -82,10 +87,10 @@ class Spectra3M:
     [Br | Bi | Br + Bi] per (frequency, K-stage, 32 output channels); ``pieces()``: the same split into three bf16 pieces per value
     in the fragment order of the bf16 matrix instruction (built on first use)."""
 
-    __slots__ = ("data", "cin", "cout", "_pieces", "_pieces_f16")
+    __slots__ = ("data", "cin", "cout", "_pieces", "_pieces_f16", "_pieces_f16_k32")
 
     def __init__(self, data: torch.Tensor, cin: int, cout: int):
-        self.data, self.cin, self.cout, self._pieces, self._pieces_f16 = data, cin, cout, None, None
+        self.data, self.cin, self.cout, self._pieces, self._pieces_f16, self._pieces_f16_k32 = data, cin, cout, None, None, None
 
     def pieces_f16(self):
         """(Bh, b_scale): the spectra times the power of two b_scale (max |.| -> at most 2^14) as two fp16 pieces per value, in the
@@ -99,6 +104,19 @@ class Spectra3M:
                                                                ops._stream()), "eqa_fft48k5_spectra3m_split_f16")
             self._pieces_f16 = (bh, scale)
         return self._pieces_f16
+
+    def pieces_f16_k32(self):
+        """(Bk, b_scale): as `pieces_f16`, in the fragment order of the 16x16x32 instruction (eqa_fft48k5_cgemm3m_f16x2_k32); built
+        on first use, the same number of bytes."""
+        if self._pieces_f16_k32 is None:
+            lib = _lib.load()
+            scale = self._pieces_f16[1] if self._pieces_f16 is not None else f16_scale(self.data)
+            bk = torch.empty(lib.eqa_fft48k5_spectra3m_f16_bytes(self.cin, self.cout) // 2, dtype=torch.int16, device=self.data.device)
+            with torch.cuda.device(self.data.device):
+                _lib.check(lib.eqa_fft48k5_spectra3m_split_f16_k32(self.data.data_ptr(), bk.data_ptr(), self.cin, self.cout, scale,
+                                                                   ops._stream()), "eqa_fft48k5_spectra3m_split_f16_k32")
+            self._pieces_f16_k32 = (bk, scale)
+        return self._pieces_f16_k32
 
     def pieces(self) -> torch.Tensor:
         if self._pieces is None:
@@ -186,7 +204,7 @@ def contract(V: torch.Tensor, B, M: int, vbound: Optional[torch.Tensor] = None) 
     """Mo[f] = V[f] . B[f] for every stored frequency: V (F, M, 2Cin) view of a pitched buffer -> Mo (F, M, 2Cout) likewise.
     ``vbound``: a device fp32 tensor whose maximum bounds every |Re|, |Im| of V (the producer's DC bins) -- admits the fp16 form."""
     dev = V.device
-    global LAST_FORM, LAST_CONTRACTION
+    global LAST_FORM, LAST_CONTRACTION, LAST_H3_MFMA
     if isinstance(B, Spectra3MC16):
         lib = _lib.load()
         assert V.shape[2] == 2 * B.cin and V.stride(1) == 2 * B.cin and V.stride(0) == lib.eqa_fft48k5_tile_pitch(M) * 2 * B.cin
@@ -202,6 +220,15 @@ def contract(V: torch.Tensor, B, M: int, vbound: Optional[torch.Tensor] = None) 
         LAST_CONTRACTION = "3m"
         form = LAST_FORM = gemm_form(B.cin, B.cout, vbound is not None)
         if form == "h3":
+            if H3_MFMA not in ("16", "32"):
+                raise RuntimeError(f"EQA_FFT_GEMM_H3_MFMA: \"16\" or \"32\" expected, not {H3_MFMA!r}")
+            LAST_H3_MFMA = H3_MFMA
+            if H3_MFMA == "16":
+                bk, b_scale = B.pieces_f16_k32()
+                _lib.check(lib.eqa_fft48k5_cgemm3m_f16x2_k32(V.data_ptr(), bk.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, vbound.data_ptr(),
+                                                             vbound.numel(), b_scale, ops._stream()),
+                           "eqa_fft48k5_cgemm3m_f16x2_k32")
+                return Mo
             bh, b_scale = B.pieces_f16()
             _lib.check(lib.eqa_fft48k5_cgemm3m_f16x2(V.data_ptr(), bh.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, vbound.data_ptr(),
                                                      vbound.numel(), b_scale, ops._stream()),

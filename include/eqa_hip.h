@@ -559,6 +559,15 @@ int64_t eqa_fft48k5_spectra3m_f16_bytes(int Cin, int Cout);
 int eqa_fft48k5_spectra3m_split_f16(const float* B3, void* Bh, int Cin, int Cout, float b_scale, void* stream);
 int eqa_fft48k5_cgemm3m_f16x2(const float* V, const void* Bh, float* Mo, int64_t M, int Cin, int Cout, const float* vbound, int nbound,
                               float b_scale, void* stream);
+/* The same fp16 two-piece contraction on v_mfma_f32_16x16x32_f16 (round 27): same operands, split, three products, 3M arithmetic and
+ * scaling; a K-stage of 32 channels, so an accumulator sums 32 k per rounding instead of 16 (the low bits of Mo differ).  Its filter
+ * operand has its own fragment order, the same size (eqa_fft48k5_spectra3m_f16_bytes):
+ *   eqa_fft48k5_spectra3m_split_f16_k32   B3 -> Bk:(F, Cin/32, Cout/32, 2 column tiles, 3 parts, 2 pieces, 64 lanes, 8) fp16 of b_scale * B3:
+ *                                         lane l, element j = channel k = 32 S + 8 (l >> 4) + j, output channel 32 c + 2 (l & 15) + column tile.
+ *   eqa_fft48k5_cgemm3m_f16x2_k32         V, Bk -> Mo; arguments and checks as eqa_fft48k5_cgemm3m_f16x2 (Cin % 32 == 0, Cout % 128 == 0). */
+int eqa_fft48k5_spectra3m_split_f16_k32(const float* B3, void* Bk, int Cin, int Cout, float b_scale, void* stream);
+int eqa_fft48k5_cgemm3m_f16x2_k32(const float* V, const void* Bk, float* Mo, int64_t M, int Cin, int Cout, const float* vbound, int nbound,
+                                  float b_scale, void* stream);
 /* The filter gradient's contraction (training), replacing the library's real [2Cin x M].[M x 2Cout] product (autograd through the
  * same R2Conv): D[f] = V[f]^T . conj(G[f]) over the M tiles in the 3-multiplication form on the fp32 MFMA.  V:(F, M|1, 2Cin),
  * G:(F, M|1, 2Cout) as eqa_fft48k5_input / _grad_transform write them; D3:(F, Cin, 2, Cout) = Dr | Di per input channel, plain

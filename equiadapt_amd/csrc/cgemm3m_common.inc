@@ -1,6 +1,8 @@
 // The wave-tile machinery of the channel contraction, shared by fft_cgemm3m_kernel (cgemm3m.hip: the fp32 matrix instruction) and
 // fft_cgemm3m_bf16_kernel (cgemm3m_bf16.hip: the bf16 pieces): which tile a wave works on, where its operands are, where the
 // finished tile goes.  The two kernels differ only in B: its element type and the bytes of one (K-stage, 32-column tile).
+// The block forms of the piece contractions (cgemm3m_block.hip, cgemm3m_block_k32.hip) take the typedefs, buf_ld, the persistent
+// grid and check_contraction_args from here; what they share beyond that is in cgemm3m_pieces.inc.
 // Included inside each file's anonymous namespace, after eqa_common.hpp.
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -128,6 +128,12 @@ inline bool allow_dynamic_lds(const void* kernel, int bytes) {
   return ok;
 }
 
+// cgemm3m_block.hip: the block form of eqa_fft48k5_cgemm3m_bf16x3 (terms = 9 / 6, Cout % 128 == 0), arguments already checked
+int launch_cgemm3m_bf16_block(int terms, const float* V, const void* Bp, float* Mo, int64_t M, int Cin, int Cout, void* stream);
+#ifdef EQA_BLK_CLOCK
+extern const void* g_blk_clock_symbol;   // cgemm3m_block.hip: the g_blk_clock of the unit whose block kernel was launched last
+#endif
+
 // pooling.hip: part (B, nseg, C, 1 + 2(k-1)) row segments -> S (B, C, k, k) fp64; used by eqa_window_sums_nhwc and by the
 // Winograd output transform fused with the window sums
 int launch_window_sums_nhwc_finalize(const float* part, double* S, int B, int C, int k, int nseg, hipStream_t stream, int sub = 1);

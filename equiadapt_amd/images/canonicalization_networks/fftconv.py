@@ -48,6 +48,7 @@ AUTO_MIN_CIN_H3 = int(os.environ.get("EQA_FFT_GEMM_AUTO_MIN_CIN_H3", "64"))
 # v_mfma_f32_16x16x32_f16 (eqa_fft48k5_cgemm3m_f16x2_k32, K-stages of 32: round 27).  Same operands, split and products; the low bits
 # of the result differ (32 k per accumulator rounding instead of 16).  The A/B switch of profiles/r27.
 H3_MFMA = os.environ.get("EQA_FFT_GEMM_H3_MFMA", "16")
+H3_ENTRIES = {"32": ("pieces_f16", "eqa_fft48k5_cgemm3m_f16x2"), "16": ("pieces_f16_k32", "eqa_fft48k5_cgemm3m_f16x2_k32")}   # H3_MFMA -> (Spectra3M's split, the entry)
 LAST_H3_MFMA = None     # ... and which of the two the most recent "h3" contraction ran on
 DCMAX_SLOTS = 256       # EQA_LIFT5_DCMAX_SLOTS (include/eqa_hip.h)
 LAST_FORM = None        # the form the most recent `contract` on the hand-written GEMM ran in (bench.py reports it)
@@ -92,31 +93,28 @@ class Spectra3M:
     def __init__(self, data: torch.Tensor, cin: int, cout: int):
         self.data, self.cin, self.cout, self._pieces, self._pieces_f16, self._pieces_f16_k32 = data, cin, cout, None, None, None
 
+    def _split_f16(self, slot: str, entry: str):
+        """The (pieces, b_scale) pair kept in ``slot``, split by the library's ``entry`` on first use.  The scale is the other fp16
+        form's once that one is built (one host synchronisation for the maximum between the two)."""
+        if getattr(self, slot) is None:
+            lib = _lib.load()
+            built = self._pieces_f16 or self._pieces_f16_k32
+            scale = built[1] if built is not None else f16_scale(self.data)
+            b = torch.empty(lib.eqa_fft48k5_spectra3m_f16_bytes(self.cin, self.cout) // 2, dtype=torch.int16, device=self.data.device)
+            with torch.cuda.device(self.data.device):
+                _lib.check(getattr(lib, entry)(self.data.data_ptr(), b.data_ptr(), self.cin, self.cout, scale, ops._stream()), entry)
+            setattr(self, slot, (b, scale))
+        return getattr(self, slot)
+
     def pieces_f16(self):
         """(Bh, b_scale): the spectra times the power of two b_scale (max |.| -> at most 2^14) as two fp16 pieces per value, in the
         fragment order of the fp16 matrix instruction (built on first use: one host synchronisation for the maximum)."""
-        if self._pieces_f16 is None:
-            lib = _lib.load()
-            scale = f16_scale(self.data)
-            bh = torch.empty(lib.eqa_fft48k5_spectra3m_f16_bytes(self.cin, self.cout) // 2, dtype=torch.int16, device=self.data.device)
-            with torch.cuda.device(self.data.device):
-                _lib.check(lib.eqa_fft48k5_spectra3m_split_f16(self.data.data_ptr(), bh.data_ptr(), self.cin, self.cout, scale,
-                                                               ops._stream()), "eqa_fft48k5_spectra3m_split_f16")
-            self._pieces_f16 = (bh, scale)
-        return self._pieces_f16
+        return self._split_f16("_pieces_f16", "eqa_fft48k5_spectra3m_split_f16")
 
     def pieces_f16_k32(self):
         """(Bk, b_scale): as `pieces_f16`, in the fragment order of the 16x16x32 instruction (eqa_fft48k5_cgemm3m_f16x2_k32); built
         on first use, the same number of bytes."""
-        if self._pieces_f16_k32 is None:
-            lib = _lib.load()
-            scale = self._pieces_f16[1] if self._pieces_f16 is not None else f16_scale(self.data)
-            bk = torch.empty(lib.eqa_fft48k5_spectra3m_f16_bytes(self.cin, self.cout) // 2, dtype=torch.int16, device=self.data.device)
-            with torch.cuda.device(self.data.device):
-                _lib.check(lib.eqa_fft48k5_spectra3m_split_f16_k32(self.data.data_ptr(), bk.data_ptr(), self.cin, self.cout, scale,
-                                                                   ops._stream()), "eqa_fft48k5_spectra3m_split_f16_k32")
-            self._pieces_f16_k32 = (bk, scale)
-        return self._pieces_f16_k32
+        return self._split_f16("_pieces_f16_k32", "eqa_fft48k5_spectra3m_split_f16_k32")
 
     def pieces(self) -> torch.Tensor:
         if self._pieces is None:
@@ -220,19 +218,13 @@ def contract(V: torch.Tensor, B, M: int, vbound: Optional[torch.Tensor] = None) 
         LAST_CONTRACTION = "3m"
         form = LAST_FORM = gemm_form(B.cin, B.cout, vbound is not None)
         if form == "h3":
-            if H3_MFMA not in ("16", "32"):
+            if H3_MFMA not in H3_ENTRIES:
                 raise RuntimeError(f"EQA_FFT_GEMM_H3_MFMA: \"16\" or \"32\" expected, not {H3_MFMA!r}")
             LAST_H3_MFMA = H3_MFMA
-            if H3_MFMA == "16":
-                bk, b_scale = B.pieces_f16_k32()
-                _lib.check(lib.eqa_fft48k5_cgemm3m_f16x2_k32(V.data_ptr(), bk.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, vbound.data_ptr(),
-                                                             vbound.numel(), b_scale, ops._stream()),
-                           "eqa_fft48k5_cgemm3m_f16x2_k32")
-                return Mo
-            bh, b_scale = B.pieces_f16()
-            _lib.check(lib.eqa_fft48k5_cgemm3m_f16x2(V.data_ptr(), bh.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, vbound.data_ptr(),
-                                                     vbound.numel(), b_scale, ops._stream()),
-                       "eqa_fft48k5_cgemm3m_f16x2")
+            pieces, entry = H3_ENTRIES[H3_MFMA]
+            bh, b_scale = getattr(B, pieces)()
+            _lib.check(getattr(lib, entry)(V.data_ptr(), bh.data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, vbound.data_ptr(),
+                                           vbound.numel(), b_scale, ops._stream()), entry)
             return Mo
         if form in ("9", "6"):
             _lib.check(lib.eqa_fft48k5_cgemm3m_bf16x3(V.data_ptr(), B.pieces().data_ptr(), Mo.data_ptr(), M, B.cin, B.cout, int(form),

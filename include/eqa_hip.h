@@ -530,7 +530,7 @@ int eqa_fft48k5_cgemm3m_supported(int Cin, int Cout);
 int64_t eqa_fft48k5_spectra3m_floats(int Cin, int Cout);
 int eqa_fft48k5_filter_spectra3m(const float* bank, float* B3, int Cout, int Cin, int correlate, void* stream);
 int eqa_fft48k5_cgemm3m(const float* V, const float* B3, float* Mo, int64_t M, int Cin, int Cout, void* stream);
-/* The same contraction on the bf16 matrix cores with fp32 semantics (csrc/cgemm3m_bf16.hip): every fp32 operand is split without
+/* The same contraction on the bf16 matrix cores with fp32 semantics (csrc/cgemm3m_bf16.hip; its block form: csrc/cgemm3m_block.hip): every fp32 operand is split without
  * error into three bf16 pieces (8 significant bits each), the product of two operands is the sum of the products of their pieces
  * -- each exact in the matrix core -- accumulated in fp32.  terms = 9: every piece product (exact products, fp32 accumulation: the
  * contract of the fp32 matrix instruction, in another summation order); terms = 6: without the three products of relative size
@@ -544,7 +544,7 @@ int eqa_fft48k5_cgemm3m(const float* V, const float* B3, float* Mo, int64_t M, i
 int64_t eqa_fft48k5_spectra3m_bf16_bytes(int Cin, int Cout);
 int eqa_fft48k5_spectra3m_split(const float* B3, void* Bp, int Cin, int Cout, void* stream);
 int eqa_fft48k5_cgemm3m_bf16x3(const float* V, const void* Bp, float* Mo, int64_t M, int Cin, int Cout, int terms, void* stream);
-/* The same contraction on TWO fp16 pieces per fp32 operand (csrc/cgemm3m_bf16.hip, TERMS = 3): x = h1 + h2 + d with h1 = rn16(s x),
+/* The same contraction on TWO fp16 pieces per fp32 operand (csrc/cgemm3m_block.hip, TERMS = 3): x = h1 + h2 + d with h1 = rn16(s x),
  * h2 = rn16(s x - h1), |d| <= 2^-23 |x| (s: a power of two that takes the operand's bound to 2^14); a product is h1 k1 + h1 k2 + h2 k1,
  * each exact in v_mfma_f32_32x32x16_f16, fp32 accumulate -- three matrix instructions per product instead of six, and closer to an
  * fp64 product than the six-product bf16 form or the fp32 instruction (profiles/r06/f16x2_gemm_check.txt, kbench_gemm_error.txt).
@@ -559,7 +559,7 @@ int64_t eqa_fft48k5_spectra3m_f16_bytes(int Cin, int Cout);
 int eqa_fft48k5_spectra3m_split_f16(const float* B3, void* Bh, int Cin, int Cout, float b_scale, void* stream);
 int eqa_fft48k5_cgemm3m_f16x2(const float* V, const void* Bh, float* Mo, int64_t M, int Cin, int Cout, const float* vbound, int nbound,
                               float b_scale, void* stream);
-/* The same fp16 two-piece contraction on v_mfma_f32_16x16x32_f16 (round 27): same operands, split, three products, 3M arithmetic and
+/* The same fp16 two-piece contraction on v_mfma_f32_16x16x32_f16 (round 27; csrc/cgemm3m_block_k32.hip): same operands, split, three products, 3M arithmetic and
  * scaling; a K-stage of 32 channels, so an accumulator sums 32 k per rounding instead of 16 (the low bits of Mo differ).  Its filter
  * operand has its own fragment order, the same size (eqa_fft48k5_spectra3m_f16_bytes):
  *   eqa_fft48k5_spectra3m_split_f16_k32   B3 -> Bk:(F, Cin/32, Cout/32, 2 column tiles, 3 parts, 2 pieces, 64 lanes, 8) fp16 of b_scale * B3:

@@ -1,6 +1,8 @@
 """eqa_fft48k5_cgemm3m_f16x2_k32: the fp16 two-piece contraction ("h3") on v_mfma_f32_16x16x32_f16 -- K-stages of 32 channels, its own
 fragment orders for A (LDS) and B (eqa_fft48k5_spectra3m_split_f16_k32), even / odd dealing of a wave's 32 columns over its two column
-tiles, 16-byte result stores.  F is fixed at 1154, so the shapes are small in M and Cin:
+tiles, 16-byte result stores.  The exact test and the row test also run the form on v_mfma_f32_32x32x16_f16 (eqa_fft48k5_cgemm3m_f16x2)
+through its C entry: the two share their argument checks, their launch and the block's walk over its tiles (csrc/cgemm3m_pieces.inc).
+F is fixed at 1154, so the shapes are small in M and Cin:
 
     (5, 64, 128)    one ragged row tile, one column group, two stages, 4-5 tiles per block: tile-to-tile hand-over of the look-ahead
     (129, 96, 128)  a second row tile of one row; three stages (odd: the B ping-pong ends on the other parity)
@@ -53,20 +55,29 @@ def _interleaved(Cr: torch.Tensor, Ci: torch.Tensor) -> torch.Tensor:
     return torch.stack([Cr, Ci], dim=3).reshape(Cr.shape[0], Cr.shape[1], -1)
 
 
-def _k32(lib, V, B3, M, bound, out=None):
-    """The new kernel through its C entry on `out` (a whole pitched buffer) or a fresh spectra buffer."""
+# the two fp16 forms: (Spectra3M's split, the contraction's entry, the split's entry); every shape has Cin % 32 == 0: both take it
+K32 = ("pieces_f16_k32", "eqa_fft48k5_cgemm3m_f16x2_k32", "eqa_fft48k5_spectra3m_split_f16_k32")     # 16x16x32: K-stages of 32
+K16 = ("pieces_f16", "eqa_fft48k5_cgemm3m_f16x2", "eqa_fft48k5_spectra3m_split_f16")                 # 32x32x16: K-stages of 16
+# the 16x16x32 cases keep the ids they had before the 32x32x16 ones joined them
+SHAPES_BY_FORM = ([pytest.param(*s, K32, id="-".join(map(str, s))) for s in SHAPES] +
+                  [pytest.param(*s, K16, id="-".join(map(str, s)) + "-32x32x16") for s in SHAPES])
+
+
+def _h3(lib, form, V, B3, M, bound, out=None):
+    """A form's kernel through its C entry on `out` (a whole pitched buffer) or a fresh spectra buffer."""
     from equiadapt_amd import _lib
     from equiadapt_amd.images.canonicalization_networks import fftconv
 
-    bk, b_scale = B3.pieces_f16_k32()
+    pieces, entry, _ = form
+    bk, b_scale = getattr(B3, pieces)()
     Mo = fftconv.spectra_buffer(M, 2 * B3.cout, V.device) if out is None else out
-    _lib.check(lib.eqa_fft48k5_cgemm3m_f16x2_k32(V.data_ptr(), bk.data_ptr(), Mo.data_ptr(), M, B3.cin, B3.cout, bound.data_ptr(),
-                                                 bound.numel(), b_scale, _stream()), "f16x2_k32")
+    _lib.check(getattr(lib, entry)(V.data_ptr(), bk.data_ptr(), Mo.data_ptr(), M, B3.cin, B3.cout, bound.data_ptr(), bound.numel(),
+                                   b_scale, _stream()), entry)
     return Mo
 
 
-@pytest.mark.parametrize("M,Cin,Cout", SHAPES)
-def test_integer_operands_give_the_fp64_product_exactly(dev, M, Cin, Cout):
+@pytest.mark.parametrize("M,Cin,Cout,form", SHAPES_BY_FORM)
+def test_integer_operands_give_the_fp64_product_exactly(dev, M, Cin, Cout, form):
     """|Re|, |Im| <= 15 on both sides, bound = 16: any error in the fragment order of A or B, in the even / odd dealing of the columns
     or in the store map shows as a wrong number.  The fp32 form on the operand this test packs must give the same product first, so a
     mistake in the packing here shows as one."""
@@ -86,7 +97,7 @@ def test_integer_operands_give_the_fp64_product_exactly(dev, M, Cin, Cout):
     _lib.check(lib.eqa_fft48k5_cgemm3m(V.data_ptr(), B3.data.data_ptr(), f32.data_ptr(), M, Cin, Cout, _stream()), "cgemm3m")
     assert torch.equal(f32, want), "the test's own packing of B3 / V"
     bound = torch.full((1,), 16.0, device=dev)
-    got = _k32(lib, V, B3, M, bound)
+    got = _h3(lib, form, V, B3, M, bound)
     bad = (got != want).nonzero()
     assert torch.equal(got, want), (bad.shape[0], bad[:4].tolist())
 
@@ -131,13 +142,13 @@ def test_random_operands_meet_the_h3_gate_and_scale_exactly(dev, M, Cin, Cout, m
         print(f"h3 k32 gate {(M, Cin, Cout)} seed {seed}: 16x16x32 max {err['h16'][0]:.3e} rms {err['h16'][1]:.3e} | 32x32x16 max "
               f"{err['h32'][0]:.3e} rms {err['h32'][1]:.3e} | f32 max {err['f32'][0]:.3e} rms {err['f32'][1]:.3e} | bound x 16: max "
               f"{err['loose'][0]:.3e} rms {err['loose'][1]:.3e}")
-        for name in ("h16", "loose"):
+        for name in ("h16", "h32", "loose"):
             assert err[name][1] <= err["f32"][1], (M, Cin, Cout, seed, name, err)
             assert err[name][0] <= 1.05 * err["f32"][0], (M, Cin, Cout, seed, name, err)
 
 
-@pytest.mark.parametrize("M,Cin,Cout", SHAPES)
-def test_rows_beyond_m_are_neither_written_nor_read_into_rows_below(dev, M, Cin, Cout):
+@pytest.mark.parametrize("M,Cin,Cout,form", SHAPES_BY_FORM)
+def test_rows_beyond_m_are_neither_written_nor_read_into_rows_below(dev, M, Cin, Cout, form):
     """Mo's pitched buffer and a guard behind it keep a sentinel outside rows < M; NaN in the pad rows of V changes no row < M."""
     import math
 
@@ -154,24 +165,26 @@ def test_rows_beyond_m_are_neither_written_nor_read_into_rows_below(dev, M, Cin,
     n, guard = fftconv.F * pitch * 2 * Cout, 128 * 2 * Cout
     flat = torch.full((n + guard,), 7.0, dtype=torch.float32, device=dev)
     full = flat[:n].view(fftconv.F, pitch, 2 * Cout)
-    _k32(lib, Vfull, B3, M, bound, out=full)
+    _h3(lib, form, Vfull, B3, M, bound, out=full)
     assert (full[:, M:] == 7.0).all() and (flat[n:] == 7.0).all()
     assert not (full[:, :M] == 7.0).any()
     Vnan = Vfull.clone()
     Vnan[:, M:] = math.nan
     again = torch.full_like(full, 7.0)
-    _k32(lib, Vnan, B3, M, bound, out=again)
+    _h3(lib, form, Vnan, B3, M, bound, out=again)
     assert torch.equal(again, full)
-    # the argument checks of the entry beside it
-    bk, b_scale = B3.pieces_f16_k32()
+    # the argument checks of the form's two entries
+    pieces, entry, split_entry = form
+    bk, b_scale = getattr(B3, pieces)()
+    contract, split = getattr(lib, entry), getattr(lib, split_entry)
     args = (Vfull.data_ptr(), bk.data_ptr(), full.data_ptr())
-    assert lib.eqa_fft48k5_cgemm3m_f16x2_k32(*args, M, Cin, Cout, None, 1, b_scale, _stream()) == -1
-    assert lib.eqa_fft48k5_cgemm3m_f16x2_k32(*args, M, Cin, Cout, bound.data_ptr(), 0, b_scale, _stream()) == -1
-    assert lib.eqa_fft48k5_cgemm3m_f16x2_k32(*args, M, Cin, Cout, bound.data_ptr(), 1, 0.0, _stream()) == -1
-    assert lib.eqa_fft48k5_cgemm3m_f16x2_k32(*args, M, Cin, 64, bound.data_ptr(), 1, b_scale, _stream()) == -3
-    assert lib.eqa_fft48k5_cgemm3m_f16x2_k32(*args, 0, Cin, Cout, bound.data_ptr(), 1, b_scale, _stream()) == 0
-    assert lib.eqa_fft48k5_spectra3m_split_f16_k32(B3.data.data_ptr(), bk.data_ptr(), Cin, Cout, 3.0, _stream()) == -1
-    assert lib.eqa_fft48k5_spectra3m_split_f16_k32(B3.data.data_ptr(), bk.data_ptr(), Cin, 64, b_scale, _stream()) == -3
+    assert contract(*args, M, Cin, Cout, None, 1, b_scale, _stream()) == -1
+    assert contract(*args, M, Cin, Cout, bound.data_ptr(), 0, b_scale, _stream()) == -1
+    assert contract(*args, M, Cin, Cout, bound.data_ptr(), 1, 0.0, _stream()) == -1
+    assert contract(*args, M, Cin, 64, bound.data_ptr(), 1, b_scale, _stream()) == -3
+    assert contract(*args, 0, Cin, Cout, bound.data_ptr(), 1, b_scale, _stream()) == 0
+    assert split(B3.data.data_ptr(), bk.data_ptr(), Cin, Cout, 3.0, _stream()) == -1
+    assert split(B3.data.data_ptr(), bk.data_ptr(), Cin, 64, b_scale, _stream()) == -3
 
 
 def test_k32_pieces_are_built_once_per_weight_version(dev, monkeypatch):

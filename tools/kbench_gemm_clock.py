@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from equiadapt_amd import _lib                                                     # noqa: E402
 from equiadapt_amd.images.canonicalization_networks import fftconv as fc          # noqa: E402
 
-STAMPED_BLOCK = 100          # BlkClock::publish (csrc/cgemm3m_bf16.hip)
+STAMPED_BLOCK = 100          # BlkClock::publish (csrc/cgemm3m_pieces.inc)
 
 
 def main():

@@ -47,6 +47,8 @@ from equiadapt_amd.images.canonicalization_networks import (  # noqa: F401
     RotationEquivariantConvLift,
     RotoReflectionEquivariantConv,
     RotoReflectionEquivariantConvLift,
+    WideResNet50Network,
+    WideResNet101Network,
     custom_equivariant_networks,
     custom_group_equivariant_layers,
     custom_nonequivariant_networks,
@@ -102,6 +104,8 @@ __all__ = [
     "ESCNNWRNEquivariantNetwork", "ESCNNWideBasic", "ESCNNWideBottleneck",
     # the ResNet-18 canonicalization network (custom_nonequivariant_networks.py:83-130; in the reference's __all__)
     "ResNet18Network",
+    # the wide ResNet canonicalization networks (custom_nonequivariant_networks.py:133-230; in the reference's __all__)
+    "WideResNet50Network", "WideResNet101Network",
 ]
 
 __version__ = "0.1.0"

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("EQA_LIB") or os.path.join(CSRC, "libeqa_hip.so")  # EQA_LIB: A/B a variant build
-SOURCES = [os.path.join(CSRC, f) for f in ("group_action.hip", "crop_resize.hip", "nearest_action.hip", "pooling.hip", "batchnorm.hip", "winograd.hip", "lift_conv.hip", "lift_conv_wide.hip", "lift_wgrad.hip", "pointcloud.hip", "vnsmall_fwd.hip", "nbody_frame.hip", "vnsmall_train.hip", "vnsmall_tail.hip", "fftconv.hip", "fft_filter.hip", "lift_fft.hip", "cgemm3m.hip", "cgemm3m_bf16.hip", "cgemm3m_block.hip", "cgemm3m_block_k32.hip", "cgemm3m_c16.hip", "smallconv.hip", "planegemm.hip", "convnet_train.hip", "fourier_act.hip", "field_norm.hip", "nbody.hip", "vn_act.hip", "gconv1x1.hip", "steer_lift.hip", "conv3x3.hip", "conv3x3_train.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("group_action.hip", "crop_resize.hip", "nearest_action.hip", "pooling.hip", "batchnorm.hip", "winograd.hip", "lift_conv.hip", "lift_conv_wide.hip", "lift_wgrad.hip", "pointcloud.hip", "vnsmall_fwd.hip", "nbody_frame.hip", "vnsmall_train.hip", "vnsmall_tail.hip", "fftconv.hip", "fft_filter.hip", "lift_fft.hip", "cgemm3m.hip", "cgemm3m_bf16.hip", "cgemm3m_block.hip", "cgemm3m_block_k32.hip", "cgemm3m_c16.hip", "smallconv.hip", "planegemm.hip", "convnet_train.hip", "fourier_act.hip", "field_norm.hip", "nbody.hip", "vn_act.hip", "gconv1x1.hip", "steer_lift.hip", "conv3x3.hip", "conv3x3_train.hip", "conv_wide.hip")]
 HEADERS = [os.path.join(CSRC, "eqa_common.hpp"), os.path.join(CSRC, "vn_common.hpp"), os.path.join(CSRC, "fourier_field.hpp"), os.path.join(CSRC, "fft48.inc"), os.path.join(CSRC, "fft_common.inc"), os.path.join(CSRC, "cgemm3m_common.inc"), os.path.join(CSRC, "cgemm3m_pieces.inc")]
 INCLUDE = os.path.join(ROOT, "include")
 
@@ -220,6 +220,10 @@ SIGNATURES = {
     "eqa_conv3x3_wgrad": (_int, [_vp] * 4 + [ctypes.c_longlong] + [_int] * 6 + [_vp]),
     "eqa_conv3x3_dgrad_supported": (_int, [ctypes.c_longlong] + [_int] * 6),
     "eqa_conv3x3_dgrad": (_int, [_vp] * 4 + [ctypes.c_longlong] + [_int] * 6 + [_vp]),
+    "eqa_convwide_supported": (_int, [ctypes.c_longlong] + [_int] * 6),
+    "eqa_convwide_ksplit": (_int, [ctypes.c_longlong] + [_int] * 6),
+    "eqa_convwide_workspace_bytes": (ctypes.c_longlong, [ctypes.c_longlong] + [_int] * 7),
+    "eqa_convwide_nhwc": (_int, [_vp] * 4 + [_int, _vp, _vp, ctypes.c_longlong] + [_int] * 7 + [_vp]),
     "eqa_bn_res_act_fwd": (_int, [_vp] * 4 + [_int, _vp, ctypes.c_int64, _int, _vp]),
     "eqa_bn_res_act_bwd_reduce": (_int, [_vp] * 5 + [_int] + [_vp] * 3 + [ctypes.c_int64, _int, _vp]),
     "eqa_bn_res_act_bwd_apply": (_int, [_vp] * 5 + [_int] + [_vp] * 7 + [ctypes.c_int64, _int, _vp]),

@@ -5,7 +5,12 @@ from equiadapt_amd.images.canonicalization_networks.custom_group_equivariant_lay
     RotoReflectionEquivariantConv,
     RotoReflectionEquivariantConvLift,
 )
-from equiadapt_amd.images.canonicalization_networks.custom_nonequivariant_networks import ConvNetwork, ResNet18Network  # noqa: F401
+from equiadapt_amd.images.canonicalization_networks.custom_nonequivariant_networks import (  # noqa: F401
+    ConvNetwork,
+    ResNet18Network,
+    WideResNet50Network,
+    WideResNet101Network,
+)
 from equiadapt_amd.images.canonicalization_networks.escnn_networks import (  # noqa: F401
     ESCNNEquivariantNetwork,
     ESCNNSteerableNetwork,

@@ -1,10 +1,12 @@
-"""ConvNetwork: the plain strided encoder the optimized canonicalizer scores group views with; ResNet18Network: the ResNet-18 one.
+"""ConvNetwork: the plain strided encoder the optimized canonicalizer scores group views with; ResNet18Network: the ResNet-18 one;
+WideResNet50Network / WideResNet101Network: the wide ResNets.
 
-Reference: equiadapt/images/canonicalization_networks/custom_nonequivariant_networks.py:8-130.
+Reference: equiadapt/images/canonicalization_networks/custom_nonequivariant_networks.py:8-230.
 Small MIOpen convolutions (PyTorch-ROCm); module / parameter names match the reference's state_dict.
 ResNet18Network's eval forward runs 19 of its 20 convolutions on eqa_conv3x3_nhwc (csrc/conv3x3.hip); with EQA_RESNET_TRAIN_KERNEL=1
 its training step runs them on that kernel, its two gradients and the eqa_bn_res_act_* block (csrc/conv3x3_train.hip).
-The wide torchvision wrappers (WideResNet50Network, WideResNet101Network) are out of scope.
+The wide ResNets' eval forward runs every convolution behind the stem on eqa_convwide_nhwc (csrc/conv_wide.hip), which splits the K
+loop over waves; their training is the plain modules.
 """
 import os
 import threading
@@ -692,3 +694,220 @@ class ResNet18Network(nn.Module):
             return self._forward_train(x)
         self.last_routes = ["plain"] * 20
         return self.resnet18(x)
+
+
+class _Bottleneck(nn.Module):
+    """The bottleneck residual block of the published wide ResNet (He et al. 2015, table 1, with the inner width doubled as in
+    Zagoruyko & Komodakis 2016 and torchvision's `wide_resnet*_2`; the stride on the 3 x 3 layer): 1 x 1 to 2 planes, 3 x 3, 1 x 1 to
+    4 planes, relu(bn3(conv3(.)) + shortcut(x)) with a 1 x 1 projection shortcut in the first block of every layer."""
+
+    def __init__(self, cin: int, planes: int, stride: int, project: bool):
+        super().__init__()
+        width = 2 * planes
+        self.conv1 = nn.Conv2d(cin, width, 1, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, 4 * planes, 1, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(4 * planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample: Optional[nn.Sequential] = None
+        if project:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, 4 * planes, 1, stride, bias=False), nn.BatchNorm2d(4 * planes))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        return self.relu(out + (x if self.downsample is None else self.downsample(x)))
+
+
+class _WideResNet(nn.Module):
+    """The wide ResNet-50-2 / ResNet-101-2 restated from the published definition, with the module names of torchvision's
+    `wide_resnet50_2` / `wide_resnet101_2` (so their state dicts load by key) and the reference's replacement head
+    `fc = Sequential(Linear(2048, out_vector_size))`."""
+
+    def __init__(self, blocks: tuple, out_vector_size: int):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        cin = 64
+        for i, (planes, count) in enumerate(zip((64, 128, 256, 512), blocks)):
+            layer = [_Bottleneck(cin, planes, 1 if i == 0 else 2, True)]
+            cin = 4 * planes
+            layer += [_Bottleneck(cin, planes, 1, False) for _ in range(count - 1)]
+            setattr(self, f"layer{i + 1}", nn.Sequential(*layer))
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Sequential(nn.Linear(2048, out_vector_size))
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1.0)
+                nn.init.constant_(m.bias, 0.0)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+
+class _WideResNetNetwork(nn.Module):
+    """A wide ResNet with a `Linear(2048, out_vector_size)` head as the canonicalization network (reference:
+    custom_nonequivariant_networks.py:133-230; `network_type: non_equivariant_wrn_50` / `non_equivariant_wrn_101`).  As there, only
+    `out_vector_size` of the constructor's arguments is used.  `self.wideresnet` is a plain torch module with torchvision's parameter
+    names, so a reference checkpoint loads by key.
+
+    Weights: the reference downloads torchvision's ImageNet weights in its constructor; this package downloads nothing.  The network
+    STARTS FROM RANDOM WEIGHTS (the published initialisation) unless a state dict is loaded -- a reference checkpoint through
+    `load_state_dict`, or a torchvision `wide_resnet50_2` / `wide_resnet101_2` state dict through `load_torchvision_state_dict`.
+
+    Routes (`last_routes`: one string per convolution in module order -- the stem, then per block conv1, conv2, conv3 and
+    downsample.0 where present: 53 / 104 entries; `last_ksplits`: the K slices of each kernel call, 0 for "lib", the stem and plain):
+      plain   `self.wideresnet(x)`: any device, dtype, training mode, autograd.  `EQA_WIDERESNET_KERNEL=0` (read per forward) forces
+              it, and everything the fused rule does not take -- training in particular -- runs here.
+      fused   ResNet18Network's rule: the module and all its batch-norms in eval, gradients disabled, a 4-D fp32 input with 3 channels
+              and B >= 1 on the device, parameters fp32, contiguous and on that device, no forward hooks on the submodules.  Every
+              batch-norm is folded into the convolution in front of it; the stem is the library's convolution on a channels-last
+              input ("lib") + relu_ + max_pool2d, used as a (B, h, w, 64) map without a copy; behind it every convolution is one call
+              of eqa_convwide_nhwc (csrc/conv_wide.hip) with bias (the folded norm), residual add and ReLU inside: a block's conv1
+              "conv1x1", conv2 "conv3x3", projection "proj", conv3 "conv1x1+res".  A layer `ops.convwide_supported` refuses, or one the
+              gate `_kernel_pays` hands to the library, runs F.conv2d on the same channels-last memory + add_ + relu_ ("lib").  The
+              tail is the mean over the pixels and F.linear.  No host synchronisation: the step can be captured into a hipGraph.
+    """
+
+    _BLOCKS: tuple = ()
+
+    def __init__(self, in_shape: tuple, out_channels: int, kernel_size: int, num_layers: int = 2, out_vector_size: int = 128):
+        super().__init__()
+        self.wideresnet = _WideResNet(self._BLOCKS, out_vector_size)
+        self.out_vector_size = out_vector_size
+        self.last_routes: List[str] = []
+        self.last_ksplits: List[int] = []
+        self._cache = DerivedCache()
+
+    def load_torchvision_state_dict(self, state_dict) -> None:
+        """Load the backbone from a torchvision `wide_resnet50_2` / `wide_resnet101_2` state dict (keys without prefix), strictly; the
+        dict's `fc.*` (1000 ImageNet classes, or any other width) is ignored and this network's head is left as it is."""
+        sd = {k: v for k, v in state_dict.items() if not k.startswith("fc.")}
+        sd.update({"fc." + k: v for k, v in self.wideresnet.fc.state_dict().items()})
+        self.wideresnet.load_state_dict(sd, strict=True)
+
+    def _blocks(self):
+        net = self.wideresnet
+        return [b for layer in (net.layer1, net.layer2, net.layer3, net.layer4) for b in layer]
+
+    def _pairs(self):
+        """(convolution, batch-norm) in module order: the stem, then per block conv1, conv2, conv3 and the shortcut where there is one."""
+        net = self.wideresnet
+        pairs = [(net.conv1, net.bn1)]
+        for b in self._blocks():
+            pairs += [(b.conv1, b.bn1), (b.conv2, b.bn2), (b.conv3, b.bn3)]
+            if b.downsample is not None:
+                pairs.append((b.downsample[0], b.downsample[1]))
+        return pairs
+
+    def _fused_applies(self, x: torch.Tensor) -> bool:
+        if self.training or torch.is_grad_enabled() or os.environ.get("EQA_WIDERESNET_KERNEL", "1") == "0":
+            return False
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and x.shape[0] >= 1):
+            return False
+        lin = self.wideresnet.fc[0]
+        for m in [m for pair in self._pairs() for m in pair] + [lin]:
+            if isinstance(m, nn.BatchNorm2d) and (m.training or m.running_mean is None or not m.affine):
+                return False
+            for t in list(m._parameters.values()) + list(m._buffers.values()):
+                if t is None or t.dtype == torch.int64:          # (an absent bias; num_batches_tracked)
+                    continue
+                if t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous():
+                    return False
+        return not any(m._forward_hooks or m._forward_pre_hooks for m in self.wideresnet.modules())
+
+    def _folded(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, pack: bool):
+        """(filters, bias) of ``bn(conv(.))`` in eval mode -- the filters channels-last, as the library's convolution wants them beside a
+        channels-last map -- and with `pack` the filters in eqa_convwide_nhwc's operand order (eqa_conv3x3_nhwc's): rebuilt when any
+        tensor that enters them has changed (common/derived.py)."""
+        def build():
+            scale, shift = bn_eval_affine(bn)
+            return (conv.weight * scale[:, None, None, None]).contiguous(memory_format=torch.channels_last), shift.contiguous()
+
+        w, b = self._cache.get(conv, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
+        if not pack:
+            return w, b
+        from equiadapt_amd import ops
+
+        return self._cache.derived(conv, (conv, "convwide"), lambda: ops.pack_conv3x3_weights(w)), b
+
+    @staticmethod
+    def _kernel_pays(pixels: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+        """The gate on shapes alone (measured: DESIGN.md section 1, "WideResNet50Network / WideResNet101Network"): the forms measured
+        slower than the library's convolution + add_ + relu_ by more than the spread between rounds go to the library from the pixel
+        count at which they were measured -- the 3 x 3 layers of 256 input channels from 36864 output pixels, of 512 from 9216, of
+        1024 from 2304, and the 1 x 1 layers with 2048 channels on either side from 2304.  Everything else, and everything smaller,
+        stays on the kernel: nothing was measured slower there."""
+        if taps == 9:
+            floor = {256: 36864, 512: 9216, 1024: 2304}.get(cin)
+            return floor is None or pixels < floor
+        return not (max(cin, cout) == 2048 and pixels >= 2304)
+
+    def _layer(self, h: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, res: Optional[torch.Tensor], relu: bool, route: str, slot: int):
+        """One convolution + folded norm (+ residual) (+ ReLU) on the (B, h, w, C) map `h`: one call of the kernel where it takes the
+        shape and pays; else the library's convolution on the same memory (a channels-last view) with add_ and relu_ ("lib")."""
+        from equiadapt_amd import ops
+
+        k, stride, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        shape = (h.shape[0], h.shape[1], h.shape[2], conv.in_channels, conv.out_channels, k * k, stride)
+        pixels = h.shape[0] * ((h.shape[1] + 2 * pad - k) // stride + 1) * ((h.shape[2] + 2 * pad - k) // stride + 1)
+        if ops.convwide_supported(*shape) and self._kernel_pays(pixels, conv.in_channels, conv.out_channels, k * k, stride):
+            wpk, b = self._folded(conv, bn, True)
+            ksplit = ops.convwide_ksplit(*shape)
+            self.last_routes[slot], self.last_ksplits[slot] = route, ksplit
+            return ops.convwide_nhwc(h, wpk, b, res, relu, k * k, stride, ksplit)
+        w, b = self._folded(conv, bn, False)
+        self.last_routes[slot], self.last_ksplits[slot] = "lib", 0
+        z = torch.nn.functional.conv2d(h.permute(0, 3, 1, 2), w, b, conv.stride, conv.padding)
+        if res is not None:
+            z.add_(res.permute(0, 3, 1, 2))
+        if relu:
+            z.relu_()
+        z = z.permute(0, 2, 3, 1)
+        return z if z.is_contiguous() else z.contiguous()
+
+    def _forward_fused(self, x: torch.Tensor) -> torch.Tensor:
+        net = self.wideresnet
+        n = len(self._pairs())
+        self.last_routes, self.last_ksplits = ["lib"] + [""] * (n - 1), [0] * n
+        w, b = self._folded(net.conv1, net.bn1, False)
+        h = torch.nn.functional.conv2d(x.contiguous(memory_format=torch.channels_last), w, b, net.conv1.stride, net.conv1.padding)
+        h = torch.nn.functional.max_pool2d(h.relu_(), 3, 2, 1).permute(0, 2, 3, 1)
+        if not h.is_contiguous():
+            h = h.contiguous()
+        slot = 1
+        for blk in self._blocks():
+            t = self._layer(h, blk.conv1, blk.bn1, None, True, "conv1x1", slot)
+            t = self._layer(t, blk.conv2, blk.bn2, None, True, "conv3x3", slot + 1)
+            if blk.downsample is not None:
+                h = self._layer(h, blk.downsample[0], blk.downsample[1], None, False, "proj", slot + 3)
+            h = self._layer(t, blk.conv3, blk.bn3, h, True, "conv1x1+res", slot + 2)
+            slot += 3 if blk.downsample is None else 4
+        lin = net.fc[0]
+        return torch.nn.functional.linear(h.mean(dim=(1, 2)), lin.weight, lin.bias)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._fused_applies(x):
+            return self._forward_fused(x)
+        n = len(self._pairs())
+        self.last_routes, self.last_ksplits = ["plain"] * n, [0] * n
+        return self.wideresnet(x)
+
+
+class WideResNet50Network(_WideResNetNetwork):
+    __doc__ = "Wide ResNet-50-2 (bottleneck blocks 3, 4, 6, 3; 53 convolutions).  " + _WideResNetNetwork.__doc__
+    _BLOCKS = (3, 4, 6, 3)
+
+
+class WideResNet101Network(_WideResNetNetwork):
+    __doc__ = "Wide ResNet-101-2 (bottleneck blocks 3, 4, 23, 3; 104 convolutions).  " + _WideResNetNetwork.__doc__
+    _BLOCKS = (3, 4, 23, 3)

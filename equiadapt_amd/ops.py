@@ -1738,6 +1738,61 @@ def conv3x3_nhwc(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, res: Op
     return y
 
 
+def convwide_supported(n: int, h: int, w: int, cin: int, cout: int, taps: int, stride: int) -> bool:
+    """Shapes and sizes eqa_convwide_nhwc takes: channel counts on the multiples of 32 from 32 to 2048; taps 9 (3 x 3, padding 1) or
+    1 (1 x 1, no padding), each at stride 1 or 2; x, y and res each inside one 32-bit buffer range (the size is part of the query)."""
+    return bool(_lib.load().eqa_convwide_supported(n, h, w, cin, cout, taps, stride))
+
+
+def convwide_ksplit(n: int, h: int, w: int, cin: int, cout: int, taps: int, stride: int) -> int:
+    """The number of K slices eqa_convwide_nhwc chooses for a shape (ksplit = 0 there): a function of the sizes alone, in
+    [1, min(16, taps cin / 32)]; 0 for a shape `convwide_supported` refuses."""
+    return int(_lib.load().eqa_convwide_ksplit(n, h, w, cin, cout, taps, stride))
+
+
+def convwide_nhwc(x: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, res: Optional[torch.Tensor] = None, relu: bool = False,
+                  taps: int = 9, stride: int = 1, ksplit: int = 0) -> torch.Tensor:
+    """y = [relu](conv(x) + bias [+ res]) (eqa_convwide_nhwc): `conv3x3_nhwc`'s function and operands on up to 2048 channels, 1 x 1
+    at stride 1 included, with the K loop cut into `ksplit` slices (0: the library's choice, `convwide_ksplit`).  ksplit 1 is one
+    launch and `conv3x3_nhwc`'s bits; more slices write partial tiles to a workspace allocated here, which a second launch adds in
+    a fixed order in fp64.  wpk = pack_conv3x3_weights(filters).  No autograd."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise RuntimeError("convwide_nhwc expects an fp32 tensor on the device")
+    wpk = _need(wpk, "wpk")
+    if wpk.dim() != 6 or wpk.shape[0] != taps or tuple(wpk.shape[3:]) != (2, 64, 4):
+        raise ValueError(f"convwide_nhwc: wpk must be pack_conv3x3_weights' ({taps}, Cin/16, Cout/32, 2, 64, 4) operand, got {tuple(wpk.shape)}")
+    Cin, Cout = wpk.shape[1] * 16, wpk.shape[2] * 32
+    if x.dim() != 4 or x.shape[3] != Cin or not x.is_contiguous():
+        raise RuntimeError(f"convwide_nhwc: x must be a contiguous (N, H, W, {Cin}) map, got {tuple(x.shape)}")
+    N, H, W = x.shape[:3]
+    bias = _need(bias, "bias")
+    if bias.numel() != Cout:
+        raise ValueError(f"convwide_nhwc: bias has {Cout} entries")
+    if not convwide_supported(N, H, W, Cin, Cout, taps, stride):
+        raise _lib.EqaLibraryError(f"eqa_convwide_nhwc does not take {N} x {H} x {W} maps of {Cin} -> {Cout} channels with taps {taps}, "
+                                   f"stride {stride} (ask convwide_supported first)")
+    if ksplit == 0:
+        ksplit = convwide_ksplit(N, H, W, Cin, Cout, taps, stride)
+    if not 1 <= ksplit <= min(16, taps * Cin // 32):
+        raise _lib.EqaLibraryError(f"eqa_convwide_nhwc: ksplit {ksplit} is outside [1, {min(16, taps * Cin // 32)}]")
+    _, _, OH, OW = _conv3x3_geom(H, W, taps, stride)
+    out_shape = (N, OH, OW, Cout)
+    p_res = None
+    if res is not None:
+        if res.dtype != torch.float32 or res.device != x.device or tuple(res.shape) != out_shape or not res.is_contiguous():
+            raise RuntimeError(f"convwide_nhwc: res must be a contiguous fp32 {out_shape} map on x's device")
+        p_res = res.data_ptr()
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    nbytes = lib.eqa_convwide_workspace_bytes(N, H, W, Cin, Cout, taps, stride, ksplit)
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    with torch.cuda.device(x.device), _timed("convwide"):
+        st = lib.eqa_convwide_nhwc(x.data_ptr(), wpk.data_ptr(), bias.data_ptr(), p_res, int(relu), y.data_ptr(),
+                                   work.data_ptr() if nbytes else None, N, H, W, Cin, Cout, taps, stride, ksplit, _stream())
+    _lib.check(st, "eqa_convwide_nhwc")
+    return y
+
+
 def _conv3x3_geom(h: int, w: int, taps: int, stride: int) -> Tuple[int, int, int, int]:
     k, pad = (3, 1) if taps == 9 else (1, 0)
     return k, pad, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1

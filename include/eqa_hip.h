@@ -1110,6 +1110,36 @@ int eqa_bn_res_act_bwd_apply(const float* gy, const float* z, const float* scale
                              const float* mean, const float* rstd, const float* gscale, const float* m1, const float* m2, float* dz,
                              float* dres, int64_t npix, int C, void* stream);
 
+/*
+ * The convolutions of WideResNet50Network / WideResNet101Network's bottleneck blocks (csrc/conv_wide.hip; reference networks:
+ * custom_nonequivariant_networks.py:133-230): eqa_conv3x3_nhwc's function, operands, layouts and packed filters
+ * (ops.pack_conv3x3_weights) on channel counts up to 2048, with the K loop split over waves as well as the output.
+ * eqa_convwide_supported: Cin, Cout multiples of 32 in [32, 2048]; taps in {1, 9} and stride in {1, 2} in all four combinations
+ * (1 x 1 at stride 1 included); the size limits of eqa_conv3x3_supported (x, y and res each <= 0xffffff00 bytes), the size test part
+ * of the query.
+ * K split.  The K loop has T = taps Cin / 16 stages of 16 channels, T / 2 stage pairs; slice i of `ksplit` takes the pairs
+ *   [floor(i (T/2) / ksplit), floor((i + 1) (T/2) / ksplit))                     admitted: 1 <= ksplit <= min(16, T/2)
+ * and accumulates them from zero in ascending order.  ksplit = 0 in the launch (and in eqa_convwide_workspace_bytes) is the
+ * library's choice, which eqa_convwide_ksplit returns (0 for a refused shape): the smallest power of two that brings
+ * (wave tiles of 64 pixels x 64 channels, 32 where Cout is an odd multiple of 32) x ksplit to 1024, the chip's wave slots, capped by
+ * the admitted range -- a function of the sizes and that constant alone, never a device query, so a call splits the same way on every
+ * machine and under graph capture.
+ *   ksplit = 1: one launch, bias, res and ReLU in the kernel's epilogue, workspace may be NULL; eqa_conv3x3_nhwc's fmaf chains in its
+ *     order: on every shape both admit the outputs are equal bit for bit.
+ *   ksplit > 1: every (wave tile, slice) stores its fp32 partial tile to workspace[slice][P][Cout]
+ *     (eqa_convwide_workspace_bytes = ksplit P Cout 4 bytes; 0 at ksplit 1, for a refused shape or a ksplit out of range); a second
+ *     launch adds the slices of an output in index order in fp64, rounds once, then adds bias and res and applies the ReLU in fp32.
+ * No atomics: two calls on the same operands give the same bits.  Rows >= P of y and of the workspace are never written.
+ * A refused shape or a ksplit out of range: EQA_ERR_UNSUPPORTED before any pointer is read.  NULL x, Wpk, bias or y, NULL workspace
+ * with ksplit > 1, y equal to x or res, workspace equal to any operand: EQA_ERR_INVALID_ARG.  Pointers 16-byte aligned (else
+ * EQA_ERR_UNSUPPORTED).  N = 0: nothing is launched.  Added without touching an existing signature: EQA_ABI_VERSION stays 3.
+ */
+int eqa_convwide_supported(long long N, int H, int W, int Cin, int Cout, int taps, int stride);
+int eqa_convwide_ksplit(long long N, int H, int W, int Cin, int Cout, int taps, int stride);
+long long eqa_convwide_workspace_bytes(long long N, int H, int W, int Cin, int Cout, int taps, int stride, int ksplit);
+int eqa_convwide_nhwc(const float* x, const float* Wpk, const float* bias, const float* res, int relu, float* y, void* workspace, long long N,
+                      int H, int W, int Cin, int Cout, int taps, int stride, int ksplit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
